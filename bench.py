@@ -22,8 +22,13 @@ the global batch of 256 sequences is FIXED ("scaling": "strong") and the layout 
          exchange. A legitimate deployment answer for this path, measured in the same run and reported in `layouts` beside the
          headline (never substituted for it); --layout dp makes it the headline.
 
-roofline.traffic (N = 1) is measured in the same run: two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) over the dominant kernel
-at the bench's shape in a child process (tools/attn_pmc_probe.py; --no-pmc quotes the committed record instead).
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline needs: set-up, W warm-up steps, graph capture,
+N timed steps, the outputs of the last step when --dump-outputs DIR is given, and the result line (metric, value, unit,
+higher_is_better, dtype, ms_per_step, config). Everything else -- roofline, allocator-order pages, the other layouts of N > 1,
+prefill TFLOPS, the GEMM leg, per-rank emulation, the engine leg, the CPU baselines -- runs with --full only.
+
+roofline.traffic (N = 1, --full) is measured in the same run: two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) over the dominant
+kernel at the bench's shape in a child process (tools/attn_pmc_probe.py; --no-pmc quotes the committed record instead).
 
 Prints ONE JSON line on rank 0.
 """
@@ -104,6 +109,14 @@ def parse():
                    help="single GPU: run ONE rank's shard of a TP=k job with the collectives stubbed (tuning aid)")
     p.add_argument("--emulate-dp", type=int, default=0,
                    help="single GPU: run ONE replica's share of the batch of a DP=k job (tuning aid, with --emulate-tp)")
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline: roofline (eager attention events, attention path in a graph, "
+                        "live PMC passes), allocator-order pages, N > 1 layouts, prefill, the GEMM leg, per-rank emulation, the "
+                        "engine leg and the CPU baselines (each still subject to its --no-* switch). Off: the run sets up, warms "
+                        "up, times --steps steps and prints the headline line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32 / float64): "
+                        "the sampled token ids and the K / V rows the step wrote into every layer's cache (rank 0's shard)")
     return p.parse_args()
 
 
@@ -480,6 +493,15 @@ def main():
         return dict(model=model, md=md, n_blocks=n_blocks, kv_caches=kv_caches, tokens=tokens, positions=positions, B=B,
                     tp_pg=tp_pg, tp_size=tp_sz, dp_size=dp_sz, nkv_l=nkv_l)
 
+    def last_step_outputs(w, tokens_out):
+        """what the last timed step computed, as a caller holds it afterwards: the sampled token ids [B] and the K / V row the
+        step wrote for every sequence into every layer's cache ([L, B, nkv, d]; at most 28 x 256 x 4 x 128 floats each, 15 MB)"""
+        slots = w["md"].slot_mapping.long()
+        rows = lambda c: c.view(-1, c.size(-2), c.size(-1)).index_select(0, slots).float()
+        return {"tokens": tokens_out.double().cpu().numpy(),
+                "kv_written_k": torch.stack([rows(kvc.k_cache) for kvc in w["kv_caches"]]).cpu().numpy(),
+                "kv_written_v": torch.stack([rows(kvc.v_cache) for kvc in w["kv_caches"]]).cpu().numpy()}
+
     def time_decode(w, steps, overlap_arm=False, overlap_graph=False):
         """warm up, capture (one graph without collectives, piecewise graphs around eager collectives, or -- one-shot kernel --
         one graph WITH them), time `steps` replays; returns the timing record and the eager step function.
@@ -502,6 +524,7 @@ def main():
         # decode runs under HIP-graph replay in the reference (runtime/dcu_graph_executor_impl.h): capture one step
         # (every op of the C ABI is capture-safe: no host sync, no allocation inside) and replay it.
         graph = None
+        out = None
         # no collective inside the step (one GPU, or data-parallel replicas): ONE graph; tensor parallel: piecewise graphs
         # overlap_graph (opt-in, --overlap-graph): the dual micro-batch step with its RCCL all-reduces captured into ONE graph -- under
         # capture launch_reduce issues the collective in place on the half's forked stream (parallel.launch_reduce), so the graph holds
@@ -516,7 +539,7 @@ def main():
             try:
                 step()
                 pw = parallel.PiecewiseGraph()
-                pw.capture(step)
+                out = pw.capture(step)
                 graph = pw
                 for _ in range(2):
                     graph.replay()
@@ -531,7 +554,7 @@ def main():
                     step()
                     g = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(g, stream=cap_stream):
-                        step()
+                        out = step()
                 torch.cuda.current_stream().wait_stream(cap_stream)
                 graph = g
                 for _ in range(2):
@@ -539,13 +562,21 @@ def main():
             except Exception as e:  # noqa: BLE001
                 print(f"[bench] graph capture failed ({e!r}); falling back to eager launches", file=sys.stderr)
                 graph = None
-        run_step = (lambda: graph.replay()) if graph is not None else step
+        held = {"out": out if graph is not None else None}   # a replayed graph refills its static output in place
+
+        def run_step():
+            if graph is not None:
+                graph.replay()
+            else:
+                held["out"] = step()
         sync_all()
         t0 = time.perf_counter()
         for _ in range(steps):
             run_step()
         sync_all()
         elapsed = max_over_ranks(time.perf_counter() - t0)
+        # read back before anything else runs on the step's buffers (the piecewise timing below replays with wrong results)
+        dumped = last_step_outputs(w, held["out"]) if (a.dump_outputs and rank == 0) else None
         if tp_pg is not None:
             tp_pg.check_agreed()   # the one-shot kernel's bounded waits: a timed-out launch on ANY rank voids the measurement and
                                    # raises on EVERY rank (collective), so all ranks take the RCCL re-timing branch together
@@ -565,7 +596,7 @@ def main():
             t_nc = max_over_ranks(time.perf_counter() - t0)
             exposed = round(max(ms - t_nc / steps * 1e3, 0.0), 4)
         return dict(ms_per_step=ms, tok_s=gbatch * steps / elapsed, graph=graph, piecewise=piecewise, exposed_comm_ms=exposed,
-                    eager_collectives=eager_collectives, dual=dual, step=step)
+                    eager_collectives=eager_collectives, dual=dual, step=step, dumped=dumped)
 
     w = build(tp_size)
     model, md, n_blocks, kv_caches, tokens, positions, B = (w["model"], w["md"], w["n_blocks"], w["kv_caches"], w["tokens"],
@@ -666,9 +697,14 @@ def main():
         sys.exit(1)
     ms_per_step, tok_s, graph, piecewise, exposed_comm_ms, dual, step = (r["ms_per_step"], r["tok_s"], r["graph"], r["piecewise"],
                                                                         r["exposed_comm_ms"], r["dual"], r["step"])
+    if a.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, arr in r["dumped"].items():
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), arr)
     # timed right after the headline (same clocks, same temperature): the page placement is the only difference
     alloc_pages = None
-    if world == 1 and tp_size == 1 and dual is None and not a.no_allocator_pages and a.emulate_tp <= 1 and a.emulate_dp <= 1:
+    if a.full and world == 1 and tp_size == 1 and dual is None and not a.no_allocator_pages and a.emulate_tp <= 1 and a.emulate_dp <= 1:
         def _alloc_pages():
             w2 = dict(w)
             w2["md"], nb2 = build_metadata(B, ctx, block_size, dev, seed=0, placement="allocator")
@@ -683,90 +719,91 @@ def main():
     collectives_per_step = (2 * len(model.layers) + 1) if tp_size > 1 else 0
     allreduce_kind = tp_pg.allreduce_kind() if (tp_pg is not None and tp_size > 1 and world > 1) else None
 
-    # roofline leg: per-launch HIP events around the dominant kernel (paged decode attention) on the launch
-    # stream, over eager steps of the same workload (events cannot be read back from inside a replayed graph)
-    record["on"] = True
-    for _ in range(min(max(a.steps, 1), 20)):     # up to 20 eager steps = 560 launches (round-5 review: 3 steps were 84)
-        step()
-    sync_all()
-    record["on"] = False
+    if a.full:
+        # roofline leg: per-launch HIP events around the dominant kernel (paged decode attention) on the launch
+        # stream, over eager steps of the same workload (events cannot be read back from inside a replayed graph)
+        record["on"] = True
+        for _ in range(min(max(a.steps, 1), 20)):     # up to 20 eager steps = 560 launches (round-5 review: 3 steps were 84)
+            step()
+        sync_all()
+        record["on"] = False
 
-    attn_ms = sum(e0.elapsed_time(e1) for e0, e1 in attn_events) / max(len(attn_events), 1)
+        attn_ms = sum(e0.elapsed_time(e1) for e0, e1 in attn_events) / max(len(attn_events), 1)
 
-    def attention_path_in_graph():
-        """the attention launches of the step by themselves -- every layer's call on its own KV cache, exactly what the layer issues
-        (the fused int8 epilogue, or attention + split-KV merge + scaled_quantize when the plan declines it) -- captured into ONE
-        graph and replayed: microseconds per layer without the host's launch gaps. For the 336-us launches of the headline the
-        eager HIP events above agree with it; for the short launches of the per-rank shapes (50-60 us) the eager figure is an
-        upper bound (the host cannot enqueue fast enough) and this is the kernel-side number."""
-        L0 = model.layers[0]
-        qa = torch.randn(B, L0.nq * L0.d, device=dev, dtype=dtype)
+        def attention_path_in_graph():
+            """the attention launches of the step by themselves -- every layer's call on its own KV cache, exactly what the layer issues
+            (the fused int8 epilogue, or attention + split-KV merge + scaled_quantize when the plan declines it) -- captured into ONE
+            graph and replayed: microseconds per layer without the host's launch gaps. For the 336-us launches of the headline the
+            eager HIP events above agree with it; for the short launches of the per-rank shapes (50-60 us) the eager figure is an
+            upper bound (the host cannot enqueue fast enough) and this is the kernel-side number."""
+            L0 = model.layers[0]
+            qa = torch.randn(B, L0.nq * L0.d, device=dev, dtype=dtype)
 
-        def run():
-            for layer, kvc in zip(model.layers, kv_caches):
-                if mode == "int8" and not a.no_fuse:
-                    layer.attention_kernel(qa, md, kvc)
-                else:
-                    ops.paged_attention(qa.unflatten(-1, (L0.nq, L0.d)), kvc.k_cache, kvc.v_cache, None, md.kv_seq_lens, md.block_table,
-                                        1, md.max_seq_len, L0.attn.scale, False, L0.attn.window_left)
-        try:
-            record["on"] = False
-            run()
-            torch.cuda.synchronize()
-            st = torch.cuda.Stream()
-            with torch.cuda.stream(st):
+            def run():
+                for layer, kvc in zip(model.layers, kv_caches):
+                    if mode == "int8" and not a.no_fuse:
+                        layer.attention_kernel(qa, md, kvc)
+                    else:
+                        ops.paged_attention(qa.unflatten(-1, (L0.nq, L0.d)), kvc.k_cache, kvc.v_cache, None, md.kv_seq_lens, md.block_table,
+                                            1, md.max_seq_len, L0.attn.scale, False, L0.attn.window_left)
+            try:
+                record["on"] = False
                 run()
                 torch.cuda.synchronize()
-                gr = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gr, stream=st):
+                st = torch.cuda.Stream()
+                with torch.cuda.stream(st):
                     run()
-                for _ in range(2):
-                    gr.replay()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(20):
-                    gr.replay()
-                e1.record()
-            torch.cuda.synchronize()
-            return e0.elapsed_time(e1) / (20 * len(model.layers))
-        except Exception as e:  # noqa: BLE001
-            print(f"[bench] attention-in-graph timing failed: {e!r}", file=sys.stderr)
-            return None
+                    torch.cuda.synchronize()
+                    gr = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(gr, stream=st):
+                        run()
+                    for _ in range(2):
+                        gr.replay()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(20):
+                        gr.replay()
+                    e1.record()
+                torch.cuda.synchronize()
+                return e0.elapsed_time(e1) / (20 * len(model.layers))
+            except Exception as e:  # noqa: BLE001
+                print(f"[bench] attention-in-graph timing failed: {e!r}", file=sys.stderr)
+                return None
 
-    attn_graph_ms = attention_path_in_graph() if world == 1 else None
-    nq_l = model.layers[0].nq
-    d = margs.head_dim
-    # algorithmic bytes per launch (SURVEY 8d): K+V of every cached token once + Q in + O out
-    attn_bytes = B * (ctx * nkv_l * d * 2 * 2 + 2 * nq_l * d * 2)
-    # Launches of ~50 us (cfg2, the per-rank shapes): HIP events around an EAGER launch also time the host's gap between the event
-    # record and the kernel's enqueue -- 55 us on a quiet host, 167 us on a busy one for the same 50-us kernel (round 6). When the
-    # eager reading is > 15 % above the same launches replayed from one graph (HIP events around the replays, on the launch
-    # stream, no host in between), the graph reading is the launch duration; both are reported.
-    eager_ms = attn_ms
-    timing = "HIP events around each eager launch"
-    if attn_graph_ms is not None and attn_graph_ms > 0 and attn_ms > 1.15 * attn_graph_ms:
-        attn_ms = attn_graph_ms
-        timing = ("HIP events around the launches replayed from one HIP graph (the eager-launch events read %.4f ms: host launch gaps)"
-                  % eager_ms)
-    achieved = attn_bytes / (attn_ms * 1e-3) / 1e9 if attn_ms > 0 else 0.0
-    traffic, traffic_source = None, None
-    if world == 1 and tp_size == 1 and a.config in ("cfg3", "cfg2") and not a.no_pmc:
-        # HBM bytes per launch of the dominant kernel from the PMC counters, collected IN THIS RUN (round-3 review, weak #12): two
-        # rocprofv3 passes (one counter each, as MI355X_MICROARCH.md prescribes) over tools/attn_pmc_probe.py = the same kernel at
-        # the same shape in a child process
-        traffic, traffic_source = live_pmc_traffic(B, ctx, nq_l, nkv_l)
-    pmc = os.path.join(ROOT, "profiles", "decode_attn_pmc.json")
-    if traffic is None and os.path.exists(pmc) and world == 1 and tp_size == 1 and a.config == "cfg3":
-        try:
-            traffic = json.load(open(pmc)).get("hbm_bytes_per_launch")
-            traffic_source = "profiles/decode_attn_pmc.json (rocprofv3 --pmc passes of an earlier run, not this run)"
-        except Exception:
-            traffic = None
+        attn_graph_ms = attention_path_in_graph() if world == 1 else None
+        nq_l = model.layers[0].nq
+        d = margs.head_dim
+        # algorithmic bytes per launch (SURVEY 8d): K+V of every cached token once + Q in + O out
+        attn_bytes = B * (ctx * nkv_l * d * 2 * 2 + 2 * nq_l * d * 2)
+        # Launches of ~50 us (cfg2, the per-rank shapes): HIP events around an EAGER launch also time the host's gap between the event
+        # record and the kernel's enqueue -- 55 us on a quiet host, 167 us on a busy one for the same 50-us kernel (round 6). When the
+        # eager reading is > 15 % above the same launches replayed from one graph (HIP events around the replays, on the launch
+        # stream, no host in between), the graph reading is the launch duration; both are reported.
+        eager_ms = attn_ms
+        timing = "HIP events around each eager launch"
+        if attn_graph_ms is not None and attn_graph_ms > 0 and attn_ms > 1.15 * attn_graph_ms:
+            attn_ms = attn_graph_ms
+            timing = ("HIP events around the launches replayed from one HIP graph (the eager-launch events read %.4f ms: host launch gaps)"
+                      % eager_ms)
+        achieved = attn_bytes / (attn_ms * 1e-3) / 1e9 if attn_ms > 0 else 0.0
+        traffic, traffic_source = None, None
+        if world == 1 and tp_size == 1 and a.config in ("cfg3", "cfg2") and not a.no_pmc:
+            # HBM bytes per launch of the dominant kernel from the PMC counters, collected IN THIS RUN (round-3 review, weak #12): two
+            # rocprofv3 passes (one counter per pass, so that no counter is multiplexed) over tools/attn_pmc_probe.py = the same kernel at
+            # the same shape in a child process
+            traffic, traffic_source = live_pmc_traffic(B, ctx, nq_l, nkv_l)
+        pmc = os.path.join(ROOT, "profiles", "decode_attn_pmc.json")
+        if traffic is None and os.path.exists(pmc) and world == 1 and tp_size == 1 and a.config == "cfg3":
+            try:
+                traffic = json.load(open(pmc)).get("hbm_bytes_per_launch")
+                traffic_source = "profiles/decode_attn_pmc.json (rocprofv3 --pmc passes of an earlier run, not this run)"
+            except Exception:
+                traffic = None
 
     # the other way N GPUs can share the batch, measured in the same run (a legitimate deployment answer, reported, not
     # substituted): N data-parallel replicas, no data-path exchange
     layouts = None
-    if world > 1 and tp_size > 1 and a.layout == "auto" and not a.no_layouts:
+    if a.full and world > 1 and tp_size > 1 and a.layout == "auto" and not a.no_layouts:
         layouts = {layout: {"ms_per_step": round(ms_per_step, 4), "tokens_per_s": round(tok_s, 2),
                             "collectives_per_step": collectives_per_step, "allreduce": allreduce_kind,
                             "exposed_comm_ms": exposed_comm_ms}}
@@ -825,15 +862,15 @@ def main():
             torch.cuda.empty_cache()
 
     prefill = None
-    if not a.no_prefill and a.config == "cfg3" and not (world > 1 and skip_arm("prefill")):
+    if a.full and not a.no_prefill and a.config == "cfg3" and not (world > 1 and skip_arm("prefill")):
         prefill = prefill_leg(model, margs, kv_caches, block_size, ctx, dev, world, tp_size, dp_size, sync_all)
 
     gemm_info = None
-    if world == 1 and tp_size == 1 and a.config == "cfg3" and not a.no_gemm:
+    if a.full and world == 1 and tp_size == 1 and a.config == "cfg3" and not a.no_gemm:
         gemm_info = gemm_leg(dev, live_pmc=not a.no_pmc)
 
     per_rank = None
-    if world == 1 and tp_size == 1 and a.config == "cfg3" and not a.no_per_rank and a.emulate_tp <= 1 and a.emulate_dp <= 1:
+    if a.full and world == 1 and tp_size == 1 and a.config == "cfg3" and not a.no_per_rank and a.emulate_tp <= 1 and a.emulate_dp <= 1:
         per_rank = per_rank_emulated()
 
     shim_info = None
@@ -841,7 +878,7 @@ def main():
         shim_info = via_shim_leg(model, margs, md, kv_caches, tokens, positions, a.steps, a.warmup)
 
     engine_info = None
-    if world == 1 and not a.no_engine and dual is None and tp_size == 1:
+    if a.full and world == 1 and not a.no_engine and dual is None and tp_size == 1:
         engine_info = engine_leg(model, kv_caches, B, ctx, block_size, n_blocks, dev, a.steps, margs)
 
     if a.micro and rank == 0:
@@ -870,14 +907,15 @@ def main():
                        "exposed_comm_ms": exposed_comm_ms,
                        "quant_fusion": not a.no_fuse, "micro_batches": 2 if dual is not None else 1,
                        "hip_graph": ("piecewise" if piecewise else True) if graph is not None else False},
-            "roofline": {"bound": "hbm", "kernel": "paged_decode_kernel (+ split-KV merge when the launch splits)",
-                         "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
-                         "bytes_per_launch": attn_bytes, "avg_launch_ms": round(attn_ms, 4), "timing": timing,
-                         "eager_events_ms": round(eager_ms, 4), "launches_timed": len(attn_events),
-                         "attention_path_ms_in_graph": None if attn_graph_ms is None else round(attn_graph_ms, 4),
-                         "attention_path_frac_in_graph": None if not attn_graph_ms else round(attn_bytes / (attn_graph_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
         }
+        if a.full:
+            out["roofline"] = {"bound": "hbm", "kernel": "paged_decode_kernel (+ split-KV merge when the launch splits)",
+                               "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
+                               "bytes_per_launch": attn_bytes, "avg_launch_ms": round(attn_ms, 4), "timing": timing,
+                               "eager_events_ms": round(eager_ms, 4), "launches_timed": len(attn_events),
+                               "attention_path_ms_in_graph": None if attn_graph_ms is None else round(attn_graph_ms, 4),
+                               "attention_path_frac_in_graph": None if not attn_graph_ms else round(attn_bytes / (attn_graph_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
         if layouts is not None:
             out["layouts"] = layouts
         if prefill is not None:
@@ -892,7 +930,7 @@ def main():
             out["per_rank_emulated"] = per_rank
         if alloc_pages is not None:
             out["allocator_order_pages"] = alloc_pages
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(margs, mode, ctx, block_size)
             if a.config == "cfg3":
                 out["cpu_baseline"]["cfg1"] = cpu_baseline_cfg1()
@@ -911,8 +949,9 @@ def per_rank_emulated():
     import subprocess
     out = {}
     for name, flags in (("tp4dp2_rank", ["--emulate-tp", "4", "--emulate-dp", "2"]), ("dp8_replica", ["--emulate-dp", "8"])):
-        cmd = [sys.executable, os.path.abspath(__file__)] + flags + ["--no-cpu-baseline", "--no-prefill", "--no-gemm", "--no-engine",
-                                                                      "--no-pmc", "--no-per-rank", "--steps", "20", "--warmup", "3"]
+        cmd = [sys.executable, os.path.abspath(__file__)] + flags + ["--full", "--no-cpu-baseline", "--no-prefill", "--no-gemm",
+                                                                      "--no-engine", "--no-pmc", "--no-per-rank", "--steps", "20",
+                                                                      "--warmup", "3"]
         try:
             res = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
             line = [l for l in res.stdout.splitlines() if l.startswith("{")][-1]

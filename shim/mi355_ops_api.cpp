@@ -356,8 +356,10 @@ std::optional<torch::Tensor> stream_scratch(std::unordered_map<StreamKey, torch:
   if (it != map.end()) return it->second;
   if (capturing()) return std::nullopt;
   torch::Tensor ws = torch::empty({bytes}, like.options().dtype(torch::kUInt8));
-  if (zero_at_rest)   // the C side zeroes it (a memset on the null stream) and keys it on the stream
+  if (zero_at_rest) {   // the C side zeroes it (a memset on the null stream) and keys it on the stream
     check(xllm_mi355_set_gemm_workspace_for_stream(cur_stream(), ws.data_ptr(), (size_t)ws.numel()), "set_gemm_workspace_for_stream");
+    check(hipDeviceSynchronize() == hipSuccess ? 0 : XM_ERR_HIP, "set_gemm_workspace_for_stream (zeroing)");   // as ops.py does
+  }
   return map.emplace(key, ws).first->second;
 }
 }  // namespace
@@ -434,9 +436,11 @@ torch::Tensor scaled_matmul(const torch::Tensor& a, const torch::Tensor& b, cons
       TORCH_CHECK(rc == XM_ERR_UNSUPPORTED || rc == XM_ERR_WORKSPACE, "scaled_matmul (packed): ", xllm_mi355_strerror(rc));
     }
   }
-  // row-major kernels: decode shapes split K through a zero-at-rest scratch registered for THIS (device, stream) -- the
-  // registration the Python mirror does in ops._ensure_gemm_workspace and the shim used to skip (round-2 review, missing #6)
-  if (M <= 512) (void)stream_scratch(g_splitk_ws, a, kSplitKBytes, true);
+  // row-major kernels: split K through a zero-at-rest scratch registered for THIS (device, stream) -- the registration the
+  // Python mirror does in ops._ensure_gemm_workspace and the shim used to skip (round-2 review, missing #6). Every M: the
+  // general kernel splits K for M > 512 too (few tiles), and a stream without its own scratch would fall back to the device's
+  // default buffer, which another stream may be summing into at the same time.
+  (void)stream_scratch(g_splitk_ws, a, kSplitKBytes, true);
   check(xllm_mi355_scaled_matmul(a.data_ptr<int8_t>(), b.data_ptr<int8_t>(), as.data_ptr<float>(),
                                  bs.data_ptr<float>(), p(bias), p(out), nullptr, M, N, K, dt(output_dtype),
                                  cur_stream()),

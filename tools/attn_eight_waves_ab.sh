@@ -14,7 +14,7 @@ for int8 in 0 1; do
   done
 done
 unset XLLM_MI355_LIB
-COMMON="--no-cpu-baseline --no-prefill --no-gemm --no-engine --no-pmc --no-per-rank --no-allocator-pages --steps 20 --warmup 3"
+COMMON="--full --no-cpu-baseline --no-prefill --no-gemm --no-engine --no-pmc --no-per-rank --no-allocator-pages --steps 20 --warmup 3"
 for flags in "--emulate-tp 4 --emulate-dp 2" "--emulate-dp 8"; do
   echo "### bench.py $flags" >> $O
   timeout 400 python bench.py $flags $COMMON 2>>gpurun_out/r06_probe2.err | tail -1 | python -c "

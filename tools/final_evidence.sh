@@ -4,15 +4,15 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/evidence
 mkdir -p $O
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 cut -c1-600 $O/bench.json
-python bench.py --config cfg2 --no-cpu-baseline 2>/dev/null | grep metric > $O/bench_cfg2.json
+python bench.py --full --config cfg2 --no-cpu-baseline 2>/dev/null | grep metric > $O/bench_cfg2.json
 python bench.py --config cfg4-slice 2>/dev/null | grep metric > $O/bench_cfg4_slice.json
 python bench.py --config cfg5-slice 2>/dev/null | grep metric > $O/bench_cfg5_slice.json
 # (the per-rank steps of the 8-GPU layouts -- TP4 x DP2 rank, DP8 replica -- are inside the default line since round 5: per_rank_emulated)
-python bench.py --via-shim --no-cpu-baseline --no-prefill --no-gemm --no-engine --no-pmc --no-per-rank 2>/dev/null | grep metric > $O/bench_via_shim.json
+python bench.py --full --via-shim --no-cpu-baseline --no-prefill --no-gemm --no-engine --no-pmc --no-per-rank 2>/dev/null | grep metric > $O/bench_via_shim.json
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $O/prof -- python $R/bench.py --no-cpu-baseline --no-engine --no-gemm --no-pmc --no-per-rank --steps 10 --warmup 3 > $O/bench_prof.log 2>&1
+rocprofv3 --kernel-trace --stats -d $O/prof -- python $R/bench.py --full --no-cpu-baseline --no-engine --no-gemm --no-pmc --no-per-rank --steps 10 --warmup 3 > $O/bench_prof.log 2>&1
 python $R/tools/rocpd_summary.py $(find $O/prof -name "*.db" | head -1) > $O/kernel_stats.txt 2>&1
 rm -rf $O/prof
 head -14 $O/kernel_stats.txt | cut -c1-170

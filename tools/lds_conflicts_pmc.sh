@@ -3,7 +3,7 @@
 R="${GRAFT_REPO_ROOT:-/root/repo}"
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/lds_pmc
-rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_INSTS_LDS SQ_ACTIVE_INST_LDS -d /tmp/lds_pmc -- python $R/bench.py ${LDS_PMC_ARGS:---no-cpu-baseline --no-engine --no-gemm --no-pmc --no-per-rank --no-allocator-pages --steps 2 --warmup 1} > /tmp/lds_pmc.log 2>&1
+rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_INSTS_LDS SQ_ACTIVE_INST_LDS -d /tmp/lds_pmc -- python $R/bench.py --full ${LDS_PMC_ARGS:---no-cpu-baseline --no-engine --no-gemm --no-pmc --no-per-rank --no-allocator-pages --steps 2 --warmup 1} > /tmp/lds_pmc.log 2>&1
 python - <<'PY'
 import glob, sqlite3
 dbs = glob.glob("/tmp/lds_pmc/**/*.db", recursive=True)
