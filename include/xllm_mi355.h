@@ -399,6 +399,13 @@ XM_API int xllm_mi355_prefill_attention(const void* q, const void* k, const void
 XM_API size_t xllm_mi355_paged_attention_workspace_bytes(int64_t batch, int64_t n_q_heads,
                                                          int64_t head_dim_v, int64_t max_q_len,
                                                          int64_t total_q_tokens);
+/* Read-only: the launch plan the decode entry points below pick for this batch (no launch, no device work). hpw = kv heads per
+ * workgroup (4, 2 or 1), nsplit = grid-level split-KV count before it is degraded to the caller's workspace (honours
+ * XLLM_MI355_DECODE_SPLITS), krows = 1 when K is fetched as whole head rows through the LDS (hpw < n_kv_heads), uniform = 1 when
+ * a 32-token tile lives in one page (block_size % 32 == 0). Any out pointer may be NULL. For tests and tools that must state
+ * which kernel arm a shape takes. */
+XM_API int xllm_mi355_paged_decode_plan(int64_t batch, int64_t n_kv_heads, int64_t block_size, int64_t max_kv_len,
+                                        int32_t* hpw, int32_t* nsplit, int32_t* krows, int32_t* uniform);
 XM_API int xllm_mi355_paged_attention(const void* q, const void* k_cache, const void* v_cache,
                                       void* out, const int32_t* cu_q, const int32_t* kv_lens,
                                       const int32_t* block_table, int64_t max_blocks, int64_t batch,

@@ -84,6 +84,21 @@ def test_decode_fusion_switches(env):
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
 
 
+@pytest.mark.parametrize("splits", ["3", "7", "32"])
+def test_decode_parity_under_forced_split_counts(splits):
+    """XLLM_MI355_DECODE_SPLITS: uneven slices (3), the generic finish / merge arm above 4 splits (7) and the largest count the
+    workspace is sized for (32), on every plan and window case of tests/test_gpu_decode_plans.py and the decode tests of
+    test_gpu_parity.py (not the must_fuse ones: a forced count changes which calls decline)"""
+    e = dict(os.environ)
+    e["XLLM_MI355_DECODE_SPLITS"] = splits
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_decode_plans.py"),
+                        os.path.join(ROOT, "tests", "test_gpu_parity.py"), "-q", "-x", "-k",
+                        "test_gpu_decode_plans or paged_decode_attention or split_kv_and_garbage or decode_window or "
+                        "rescale_branch", "-p", "no:cacheprovider"], cwd=ROOT, env=e, capture_output=True, text=True,
+                       timeout=900)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+
+
 @pytest.mark.parametrize("env", [{}, {"XLLM_MI355_P8": "1"}, {"XLLM_MI355_P8": "0"}, {"XLLM_MI355_PACKED": "0"},
                                  {"XLLM_MI355_P8": "0", "XLLM_MI355_SKINNY_DISABLE": "1"}],
                          ids=["default", "p8_forced", "p8_off", "packed_off", "general_only"])

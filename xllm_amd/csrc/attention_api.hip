@@ -102,6 +102,17 @@ size_t xllm_mi355_paged_attention_workspace_bytes(int64_t batch, int64_t n_q_hea
   return (size_t)batch * n_q_heads * 32 * (head_dim_v + 2) * sizeof(float);  // 32 = max split-KV count
 }
 
+int xllm_mi355_paged_decode_plan(int64_t batch, int64_t n_kv_heads, int64_t block_size, int64_t max_kv_len, int32_t* hpw,
+                                 int32_t* nsplit, int32_t* krows, int32_t* uniform) {
+  if (batch <= 0 || n_kv_heads <= 0 || block_size <= 0 || max_kv_len < 0) return XM_ERR_INVALID;
+  const int h = decode_heads_per_wg(batch, n_kv_heads);
+  if (hpw) *hpw = h;
+  if (nsplit) *nsplit = decode_num_splits(batch, n_kv_heads, h, max_kv_len);
+  if (krows) *krows = h < n_kv_heads ? 1 : 0;            // launch_paged_decode: krows
+  if (uniform) *uniform = block_size % 32 == 0 ? 1 : 0;  // launch_paged_decode: block_size % kTile == 0
+  return XM_OK;
+}
+
 int xllm_mi355_paged_attention(const void* q, const void* k_cache, const void* v_cache, void* out,
                                const int32_t* cu_q, const int32_t* kv_lens, const int32_t* block_table,
                                int64_t max_blocks, int64_t batch, int64_t total_q_tokens, int64_t n_q_heads,

@@ -254,12 +254,14 @@ __global__ __launch_bounds__(256, DEEP ? 1 : 2) void paged_decode_kernel(
         for (int kk = 0; kk < KK; ++kk) kf[blk][kk] = kr[blk][kk];
     }
 
-    // ---- V tile -> wave-private LDS (row major, padded rows); invalid rows zeroed (0 * NaN guard)
+    // ---- V tile -> wave-private LDS (row major, padded rows); invalid rows zeroed (0 * NaN guard): the tail past kv_len and,
+    //      in the window's edge tile, the rows below t_lo -- both meet p = 0 in the PV MFMA and may hold anything
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const int r = i * TPI + lane / CH;
       u32x4 v = vr[i];
-      if (partial && (t0 + r >= kv_len)) v = u32x4{0u, 0u, 0u, 0u};
+      // one unsigned range test for t_lo <= t0 + r < kv_len (t_lo <= kv_len always; a row below t_lo wraps to a huge value)
+      if (partial && (unsigned)(t0 - t_lo + r) >= (unsigned)(kv_len - t_lo)) v = u32x4{0u, 0u, 0u, 0u};
       *reinterpret_cast<u32x4*>(my_lds + r * RSB + (lane % CH) * 16) = v;
     }
 
