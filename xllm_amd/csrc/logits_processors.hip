@@ -81,13 +81,15 @@ __device__ __forceinline__ uint32_t lp_key(float x) {
 __device__ __forceinline__ float lp_unkey(uint32_t k) {
   return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
-// probability mass of a logit in 2^-40 fixed point (x <= row max: the mass is in (0, 1]). The mass is ALWAYS fp32 exp(x - max):
-// for fp32 logits (what the engine passes, engine.py: logits(hidden).float()) this is the reference's softmax -> fp32 cumsum; for
-// 16-bit logits the reference's one-of-them branch runs softmax in the logits dtype first (logits_utils.cpp:145), i.e. rounds each
-// probability to 16 bit before the fp32 cumsum, so its cut-off rank can differ from this kernel's by the ranks whose cumulative
-// mass lies within that rounding of p. Parity with the sorting reference is therefore asserted for fp32 logits (exact up to
-// boundary cases) and for 16-bit logits only up to such boundary ranks (tests/test_gpu_parity.py::
-// test_apply_top_k_top_p_matches_the_sorting_reference).
+// probability mass of a logit in 2^-40 fixed point (x <= row max: the mass is in (0, 1]). The mass is ALWAYS fp32 exp(x - max),
+// whatever the logits dtype: the engine's random-sampling step passes the lm_head's 16-bit logits (ops.sample_top_k_top_p), tools
+// and tests also fp32. On the values the kernel ranks (temperature applied, rounded to the logits dtype) that is the reference's
+// softmax -> fp32 cumsum carried out exactly: integer sums are order-free, and the error left is __expf's and the 2^-40 granule,
+// about 1e-6 of the total. The reference's one-of-them branch on a 16-bit TENSOR runs softmax in that dtype first
+// (logits_utils.cpp:145), i.e. rounds each probability to 16 bit before the cumsum; that rounding is not reproduced.
+// Parity held (tests/test_gpu_logits_processors.py, f32 / bf16 / f16): the surviving set EQUALS the one a dense float64
+// restatement keeps whenever p is clear of the cumulative-probability steps (the reference's fp32 sort + cumsum keeps that set
+// too, tests/test_logits_reference.py); with p placed on a step the cut may move only across ranks whose prefix is within 2e-5 of p.
 // (a NaN logit has no mass: the float -> integer conversion of a NaN is undefined behaviour)
 __device__ __forceinline__ unsigned long long lp_mass(float x, float mx) {
   const float e = __expf(x - mx) * 1099511627776.0f;
