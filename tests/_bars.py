@@ -7,6 +7,16 @@ def rel_l2(a, b):
     return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
 
 
+def assert_attn_close(got, ref, rel=1e-3):
+    """attention with fp32-P accuracy: relative L2 over the tensor <= rel, and element-wise within 2 bf16 ulp of the row maximum"""
+    got, ref = got.float().cpu(), ref.float().cpu()
+    assert torch.isfinite(got).all()
+    err = (got - ref).norm() / ref.norm().clamp_min(1e-30)
+    assert err <= rel, f"relative L2 error {err:.3e} > {rel}"
+    scale = ref.abs().amax(-1, keepdim=True).clamp_min(1e-30)
+    assert ((got - ref).abs() <= 2 * 2.0 ** -8 * scale + 1e-30).all(), f"max abs {(got - ref).abs().max()}"
+
+
 FLASH_BAR = 1e-3   # north_star's bf16 tolerance, held ABSOLUTELY against the oracle mode that has the kernel's cast point
 
 

@@ -39,13 +39,7 @@ def rel_l2(got, ref):
     return float((got - ref).norm() / ref.norm().clamp_min(1e-300))
 
 
-def assert_attn_close(got, ref, rel=1e-3):
-    got, ref = got.float().cpu(), ref.float().cpu()
-    assert torch.isfinite(got).all()
-    err = (got - ref).norm() / ref.norm().clamp_min(1e-30)
-    assert err <= rel, f"relative L2 error {err:.3e} > {rel}"
-    scale = ref.abs().amax(-1, keepdim=True).clamp_min(1e-30)
-    assert ((got - ref).abs() <= 2 * 2.0 ** -8 * scale + 1e-30).all(), f"max abs {(got - ref).abs().max()}"
+from _bars import assert_attn_close  # noqa: E402,F401  (shared with the CPU-side case helpers; other test files import it from here)
 
 
 def assert_prefill_close(out, q, k, v, cu, scale):

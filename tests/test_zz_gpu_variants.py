@@ -56,7 +56,8 @@ def test_prefill_parity_under_kernel_selector(env):
     e = dict(os.environ)
     e.update(env)
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_parity.py"),
-                        os.path.join(ROOT, "tests", "test_gpu_fullsize.py"), "-q", "-x", "-k",
+                        os.path.join(ROOT, "tests", "test_gpu_fullsize.py"),
+                        os.path.join(ROOT, "tests", "test_gpu_prefill_masks.py"), "-q", "-x", "-k",
                         "prefill or chunked or model", "-p", "no:cacheprovider"], cwd=ROOT, env=e, capture_output=True,
                        text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]

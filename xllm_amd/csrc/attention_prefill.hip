@@ -156,7 +156,10 @@ __global__ __launch_bounds__(256, 2) void flash_prefill_kernel(
       const int c = tid + i * 256, row = c / CH, col = c % CH;
       *reinterpret_cast<uint4*>(&lds[buf][row * RSK + col * 16]) = rk[i];
       uint4 vv = rv[i];
-      if (t0 + row >= kv_len) vv = make_uint4(0, 0, 0, 0);  // 0 * NaN guard for masked keys
+      // 0 * NaN guard for keys every query of the block masks: the rows past kv_len and, in the window's edge tile, the rows
+      // below lo_tok (with pages shorter than the tile they may come from a page the cache has already recycled). One
+      // unsigned range test for lo_tok <= t0 + row < kv_len (lo_tok <= kv_len always; a row below lo_tok wraps to a huge value)
+      if ((unsigned)(t0 + row - lo_tok) >= (unsigned)(kv_len - lo_tok)) vv = make_uint4(0, 0, 0, 0);
       *reinterpret_cast<uint4*>(&lds[buf][kPfTile * RSK + row * RSV + col * 16]) = vv;
     }
   };
