@@ -72,7 +72,7 @@ __global__ __launch_bounds__(256, DEEP ? 1 : 2) void paged_decode_kernel(
     float* __restrict__ part_o, float* __restrict__ part_ml, const int32_t* __restrict__ cu_q,
     const int32_t* __restrict__ kv_lens, const int32_t* __restrict__ block_table, int max_blocks, int nq,
     int nkv, int block_size, int64_t q_stride, float scale_log2, int nsplit, int hpw, int window_left,
-    int8_t* __restrict__ out_q, float* __restrict__ out_scale, int part_mode) {
+    int8_t* __restrict__ out_q, float* __restrict__ out_scale, int part_mode, int wide_store) {
   using TR = AttnTraits<T>;
   using x8 = typename TR::x8;
   using x4 = typename TR::x4;
@@ -377,68 +377,112 @@ __global__ __launch_bounds__(256, DEEP ? 1 : 2) void paged_decode_kernel(
     if (g == 0) { ml_sh[wave][p16][0] = m_run; ml_sh[wave][p16][1] = l_run; }
   }
   __syncthreads();
+  // One pass over work items (head slot h_s, live query head qq < G, 8 consecutive d): hpw * G * D / 8 of them, at most 1024, so
+  // a thread takes at most 4 and padded query heads are never visited. Per item (m, l) of each contributing wave is read once,
+  // m*, f = exp2(m - m*) and l are formed once per head, and O comes in as two 16-byte LDS reads per wave; the 8 values are
+  // the expressions of the element-wise loop this replaces, in the same order over sb, so every exit is bit-identical to it.
+  // wide_store (host, per launch): the output bases admit 16-byte (16-bit out, part_o) / 8-byte (int8) stores.
   const int64_t qtok = cu_q ? cu_q[b] : b;
-  if (out_q) {
-    // N1 fusion: the workgroup holds ALL heads of this token (host guarantees nsplit == 1 and one head group),
-    // so the per-token int8 quantisation that feeds o_proj (scaled_quantize of the 16-bit output) is done here:
-    // pass 1 = 16-bit output + |max|, pass 2 = quantise. Bit-identical to paged_attention -> scaled_quantize.
-    __shared__ float red[32];
-    auto value = [&](int e, int& head, int& d) -> float {
-      const int h_s = e / (16 * D), qq = (e / D) & 15;
-      d = e % D;
-      head = h_s * G + qq;
-      if (qq >= G) return 0.0f;
+  constexpr int DPI = D / 8;  // items per head
+  const int nitems = hpw * G * DPI;
+  __shared__ float red[32];
+  float val[4][8];  // int8 form: the rounded values wait here for the row maximum
+  float amax = 0.0f;
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int item = threadIdx.x + it * 256;
+    if (item < nitems) {
+      const int hq = item / DPI, d = (item % DPI) * 8;
+      const int h_s = hq / G, qq = hq - h_s * G;
+      float mw[4], lw[4];
       float m_star = kNegBig;
-      for (int sb = 0; sb < nsub; ++sb) m_star = fmaxf(m_star, ml_sh[sb * hpw + h_s][qq][0]);
-      float o = 0.0f, l = 0.0f;
-      for (int sb = 0; sb < nsub; ++sb) {
-        const int w = sb * hpw + h_s;
-        const float f = exp2f(ml_sh[w][qq][0] - m_star);
-        o += f * reinterpret_cast<const float*>(lds + w * WAVE_LDS)[qq * D + d];
-        l += f * ml_sh[w][qq][1];
+#pragma unroll
+      for (int sb = 0; sb < 4; ++sb)
+        if (sb < nsub) {
+          const float2 ml = *reinterpret_cast<const float2*>(&ml_sh[sb * hpw + h_s][qq][0]);
+          mw[sb] = ml.x;
+          lw[sb] = ml.y;
+          m_star = fmaxf(m_star, ml.x);
+        }
+      float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      float l = 0.0f;
+#pragma unroll
+      for (int sb = 0; sb < 4; ++sb)
+        if (sb < nsub) {
+          const float f = exp2f(mw[sb] - m_star);
+          const float* op = reinterpret_cast<const float*>(lds + (sb * hpw + h_s) * WAVE_LDS) + qq * D + d;
+          const f32x4_t oa = *reinterpret_cast<const f32x4_t*>(op), ob = *reinterpret_cast<const f32x4_t*>(op + 4);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            o[j] += f * oa[j];
+            o[4 + j] += f * ob[j];
+          }
+          l += f * lw[sb];
+        }
+      const int head = (hg * hpw + h_s) * G + qq;
+      if (part_mode) {  // grid-level split-KV, or a finishing kernel that wants (o, m, l) of the whole range (nsplit == 1)
+        const int64_t pi = ((int64_t)b * nq + head) * nsplit + split;
+        float* po = part_o + pi * D + d;
+        if (wide_store) {
+          *reinterpret_cast<f32x4_t*>(po) = f32x4_t{o[0], o[1], o[2], o[3]};
+          *reinterpret_cast<f32x4_t*>(po + 4) = f32x4_t{o[4], o[5], o[6], o[7]};
+        } else {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) po[j] = o[j];
+        }
+        if (d == 0) { part_ml[pi * 2] = m_star; part_ml[pi * 2 + 1] = l; }
+      } else {
+        u32x4 pk = {0u, 0u, 0u, 0u};
+        T t[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          t[j] = from_f32<T>(l > 0.0f ? o[j] / l : 0.0f);
+          uint16_t bits;
+          __builtin_memcpy(&bits, &t[j], 2);
+          pk[j >> 1] |= (unsigned)bits << ((j & 1) * 16);
+          val[it][j] = to_f32<T>(t[j]);
+          amax = fmaxf(amax, fabsf(val[it][j]));
+        }
+        if (out) {  // the int8 form's 16-bit copy is optional
+          T* op16 = out + qtok * (int64_t)nq * D + (int64_t)head * D + d;
+          if (wide_store) *reinterpret_cast<u32x4*>(op16) = pk;
+          else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) op16[j] = t[j];
+          }
+        }
       }
-      return r16<T>(l > 0.0f ? o / l : 0.0f);
-    };
-    float amax = 0.0f;
-    for (int e = threadIdx.x; e < hpw * 16 * D; e += 256) {
-      int head, d;
-      const float v = value(e, head, d);
-      if (((e / D) & 15) >= G) continue;
-      amax = fmaxf(amax, fabsf(v));
-      if (out) out[qtok * (int64_t)nq * D + (int64_t)head * D + d] = from_f32<T>(v);
-    }
-    amax = block_max(amax, red);
-    const float qinv = (amax > 1e-10f) ? 127.0f / amax : 0.0f;
-    for (int e = threadIdx.x; e < hpw * 16 * D; e += 256) {
-      int head, d;
-      const float v = value(e, head, d);
-      if (((e / D) & 15) >= G) continue;
-      out_q[qtok * (int64_t)nq * D + (int64_t)head * D + d] = (int8_t)fmaxf(-127.0f, fminf(127.0f, rintf(v * qinv)));
-    }
-    if (threadIdx.x == 0) out_scale[qtok] = amax / 127.0f;
-    return;
-  }
-  for (int e = threadIdx.x; e < hpw * 16 * D; e += 256) {
-    const int h_s = e / (16 * D), qq = (e / D) & 15, d = e % D;
-    if (qq >= G) continue;
-    float m_star = kNegBig;
-    for (int sb = 0; sb < nsub; ++sb) m_star = fmaxf(m_star, ml_sh[sb * hpw + h_s][qq][0]);
-    float o = 0.0f, l = 0.0f;
-    for (int sb = 0; sb < nsub; ++sb) {
-      const int w = sb * hpw + h_s;
-      const float f = exp2f(ml_sh[w][qq][0] - m_star);
-      o += f * reinterpret_cast<const float*>(lds + w * WAVE_LDS)[qq * D + d];
-      l += f * ml_sh[w][qq][1];
-    }
-    const int head = (hg * hpw + h_s) * G + qq;
-    if (!part_mode) {
-      out[qtok * (int64_t)nq * D + (int64_t)head * D + d] = from_f32<T>(l > 0.0f ? o / l : 0.0f);
-    } else {  // grid-level split-KV, or a finishing kernel that wants (o, m, l) of the whole range (nsplit == 1)
-      const int64_t pi = ((int64_t)b * nq + head) * nsplit + split;
-      part_o[pi * D + d] = o;
-      if (d == 0) { part_ml[pi * 2] = m_star; part_ml[pi * 2 + 1] = l; }
     }
   }
+  if (!out_q) return;
+  // N1 fusion: the workgroup holds ALL heads of this token (host guarantees nsplit == 1 and one head group), so the per-token
+  // int8 quantisation that feeds o_proj (scaled_quantize of the 16-bit output) is done here, from the registers above.
+  // Bit-identical to paged_attention -> scaled_quantize.
+  amax = block_max(amax, red);
+  const float qinv = (amax > 1e-10f) ? 127.0f / amax : 0.0f;
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int item = threadIdx.x + it * 256;
+    if (item < nitems) {
+      unsigned lo = 0u, hi = 0u;
+      int8_t q8[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        q8[j] = (int8_t)fmaxf(-127.0f, fminf(127.0f, rintf(val[it][j] * qinv)));
+        const unsigned byte = (unsigned)(uint8_t)q8[j] << ((j & 3) * 8);
+        if (j < 4) lo |= byte;
+        else hi |= byte;
+      }
+      // item * 8 == head * D + d here: one head group (hg == 0), heads and their d chunks in item order
+      int8_t* oq = out_q + qtok * (int64_t)nq * D + (int64_t)item * 8;
+      if (wide_store) *reinterpret_cast<uint2*>(oq) = make_uint2(lo, hi);
+      else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) oq[j] = q8[j];
+      }
+    }
+  }
+  if (threadIdx.x == 0) out_scale[qtok] = amax / 127.0f;
 }
 
 // merge of the grid-level split-KV partials: one workgroup (D threads) per (sequence, head)
@@ -609,11 +653,14 @@ int launch_paged_decode(const void* q, const void* kc, const void* vc, void* out
   // tuning arm (XLLM_MI355_DECODE_EXCL=1, -DXM_TUNING flavour only): grids of at most one workgroup per CU reserve enough extra LDS that two
   // workgroups cannot share a CU, so the dispatcher has to spread them over all 256
   const size_t dyn = (decode_exclusive_cu() && grid.x <= 256) ? 48 * 1024 : 0;
+  // the epilogue's stores: 16 bytes per work item (16-bit out, fp32 partials) and 8 bytes (int8) when the bases allow it --
+  // rows are nq * D elements with D a multiple of 64, so only the pointers decide; otherwise element-wise, same loop
+  const int wide_store = (part_mode ? (uintptr_t)part_o % 16 == 0 : (uintptr_t)out % 16 == 0) && (uintptr_t)kq % 8 == 0;
   const bool krows = hpw < nkv;   // the wave's head is a strided slice of rows whose other heads are elsewhere (see issue_loads)
 #define XM_DECODE_LAUNCH(UNI_, DEEP_, KROWS_, DYN_)                                                                        \
   hipLaunchKernelGGL((paged_decode_kernel<T, D, UNI_, DEEP_, KROWS_>), grid, dim3(256), DYN_, s, (const T*)q, (const T*)kc, \
                      (const T*)vc, (T*)out, part_o, part_ml, cu_q, kv_lens, block_table, (int)max_blocks, (int)nq,        \
-                     (int)nkv, (int)block_size, q_stride, scale_log2, nsplit, hpw, wl, kq, kqs, part_mode)
+                     (int)nkv, (int)block_size, q_stride, scale_log2, nsplit, hpw, wl, kq, kqs, part_mode, wide_store)
 #ifdef XM_TUNING  /* the three-stage arm (round-1 A/B loser) exists only in the tuning flavour */
   if (block_size % kTile == 0 && decode_deep_prefetch()) XM_DECODE_LAUNCH(true, true, false, dyn);
   else
