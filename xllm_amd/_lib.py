@@ -47,6 +47,7 @@ _SIGS = {
     "xllm_mi355_host_plan_input_buffer": ([C.POINTER(HostBufferEntry), i64, u64, C.POINTER(u64)], ci),
     "xllm_mi355_host_pack_input_buffer": ([C.POINTER(HostBufferEntry), i64, vp, u64], ci),
     "xllm_mi355_host_build_batch": ([vp, vp, vp, vp, i64, i64, C.POINTER(HostBatch)], ci),
+    "xllm_mi355_host_shared_prefix_groups": ([vp, i64, vp, i64, i64, i64, i64, vp, vp, vp], ci),
     "xllm_mi355_abi_version": ([], ci),
     "xllm_mi355_build_digest": ([], C.c_char_p),
     "xllm_mi355_block_copy": ([vp, vp, vp, vp, vp, i64, i64, i64, i64, vp], ci),
@@ -115,6 +116,10 @@ _SIGS = {
     "xllm_mi355_paged_decode_plan": ([i64, i64, i64, i64, vp, vp, vp, vp], ci),
     "xllm_mi355_paged_attention": ([vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64,
                                     i64, f32, ci, i64, ci, vp, sz, vp], ci),
+    "xllm_mi355_shared_prefix_decode_workspace_bytes": ([i64, i64, i64, i64, i64, i64], sz),
+    "xllm_mi355_shared_prefix_decode_plan": ([i64, i64, i64, i64, i64, i64, vp, vp, vp, vp], ci),
+    "xllm_mi355_paged_decode_attention_shared_prefix": ([vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, i64, i64, i64, i64, i64, i64,
+                                                         i64, i64, i64, f32, ci, ci, vp, sz, vp], ci),
 }
 # entry points declared in the header but implemented in a later build step are bound lazily
 _OPTIONAL = {

@@ -7,6 +7,7 @@ layers/dcu/flash_attention.cpp:291-376: write K/V at slot_mapping, then prefill 
 """
 from __future__ import annotations
 
+import ctypes as C
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -62,6 +63,38 @@ def cache_slots(block_ids, block_size: int, pos_start: int, pos_end: int) -> tor
     _lib.check(_lib.lib().xllm_mi355_host_cache_slots(blocks.data_ptr(), blocks.numel(), block_size, pos_start, pos_end,
                                                       out.data_ptr()), "host_cache_slots")
     return out
+
+
+# Defaults of shared_prefix_groups, from the measured table of profiles/shared_prefix_decode.txt (DESIGN.md "shared-prefix
+# decode"): the smallest measured point at which ops.paged_attention_shared_prefix beats ops.paged_attention by more than the
+# run-to-run spread of paged_attention itself. One measured point above these thresholds still loses: ONE group of 256 sequences at
+# 512 shared tokens is 2.4 % slower than paged_attention (which already finds that one small prefix in the caches); from 2048
+# tokens on every measured grouping wins. Groups below 16 and prefixes between the measured ones are not measured.
+SHARED_PREFIX_MIN_GROUP = 16
+SHARED_PREFIX_MIN_PREFIX_TOKENS = 512
+
+
+def shared_prefix_groups(block_table_cpu, kv_lens_cpu, block_size: int, min_group: Optional[int] = None,
+                         min_prefix_blocks: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The groups ops.paged_attention_shared_prefix takes (xllm_mi355_host_shared_prefix_groups): contiguous runs of rows of the
+    host block table [B, max_blocks] that start with the same full pages, in batch order. Returns (group_cu int32 [n_groups + 1],
+    group_prefix_blocks int32 [n_groups]) on the host; a run shorter than min_group or sharing fewer than min_prefix_blocks pages
+    leaves every row a group of its own without a shared stage."""
+    if min_group is None:
+        min_group = SHARED_PREFIX_MIN_GROUP
+    if min_prefix_blocks is None:
+        min_prefix_blocks = max(1, -(-SHARED_PREFIX_MIN_PREFIX_TOKENS // block_size))
+    bt = torch.as_tensor(block_table_cpu, dtype=torch.int32).contiguous()
+    lens = torch.as_tensor(kv_lens_cpu, dtype=torch.int32).contiguous()
+    B = lens.numel()
+    bt = bt.view(B, -1) if B else bt.reshape(0, 0)
+    cu = torch.empty(B + 1, dtype=torch.int32)
+    pre = torch.empty(max(B, 1), dtype=torch.int32)
+    n = C.c_int32(0)
+    _lib.check(_lib.lib().xllm_mi355_host_shared_prefix_groups(bt.data_ptr(), bt.size(1), lens.data_ptr(), B, block_size,
+                                                               min_group, min_prefix_blocks, cu.data_ptr(), pre.data_ptr(),
+                                                               C.addressof(n)), "host_shared_prefix_groups")
+    return cu[:n.value + 1].clone(), pre[:n.value].clone()
 
 
 def build_batch_input(n_kv_cache_tokens, seq_lens, block_ids_per_seq, block_size: int) -> BatchInput:

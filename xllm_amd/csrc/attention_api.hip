@@ -3,6 +3,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "xllm_mi355_shared_prefix.h"
 
 namespace xm {
 
@@ -12,6 +13,16 @@ int launch_paged_decode(const void* q, const void* kc, const void* vc, void* out
                         int64_t nq, int64_t nkv, int64_t block_size, int64_t q_stride, int64_t max_kv_len,
                         float scale, int64_t window_left, void* workspace, size_t ws_bytes, hipStream_t s,
                         int8_t* out_q, float* out_scale);
+
+// attention_shared_prefix.hip
+template <typename T, int D>
+int launch_shared_prefix_decode(const void* q, const void* kc, const void* vc, void* out, const int32_t* kv_lens,
+                                const int32_t* block_table, int64_t max_blocks, const int32_t* group_cu,
+                                const int32_t* group_prefix_blocks, int64_t n_groups, int64_t batch, int64_t nq, int64_t nkv,
+                                int64_t block_size, int64_t q_stride, float scale, int suffix_hpw, int suffix_nsplit,
+                                int prefix_nsplit, void* workspace, hipStream_t s);
+int shared_prefix_rows_per_tile();
+int shared_prefix_num_splits(int64_t batch, int64_t nq, int64_t nkv, int64_t block_size, int64_t max_prefix_blocks);
 
 template <typename T, int D, bool PAGED>
 int launch_flash_prefill(const void* q, const void* k, const void* v, void* out, const int32_t* cu_q,
@@ -188,6 +199,80 @@ int xllm_mi355_paged_decode_attention_int8_ws(const void* q, const void* k_cache
   if (dtype == XM_F16 && head_dim == 128) XM_DECODEQ(f16_t, 128);
   if (dtype == XM_F16 && head_dim == 64) XM_DECODEQ(f16_t, 64);
 #undef XM_DECODEQ
+  return XM_ERR_UNSUPPORTED;
+}
+
+// ---- shared-prefix decode (attention_shared_prefix.hip). The workspace holds the metadata of the prologue and one (o, m, l) row
+// of head_dim + 2 floats per (sequence, head, split) of either stage. It follows the planners instead of their caps (32 and 8
+// splits), by bounds that grow with every argument, so the size is monotone although batch * splits(batch) is not:
+//  * suffix stage: decode_num_splits gives min(ceil(256 / workgroups), tiles / (8 * nsub), 32) with workgroups >= batch * nkv / 4,
+//    so batch * splits <= min(batch * min(32, max(1, tiles / 8)), ceil(1024 / nkv) + batch); a forced count
+//    (XLLM_MI355_DECODE_SPLITS) takes batch * min(count, 32);
+//  * shared stage: batch * 8, the cap of shared_prefix_num_splits and of a forced prefix_splits.
+size_t xllm_mi355_shared_prefix_decode_workspace_bytes(int64_t batch, int64_t n_q_heads, int64_t head_dim, int64_t max_blocks,
+                                                       int64_t max_kv_len, int64_t n_kv_heads) {
+  if (batch <= 0 || n_q_heads <= 0 || head_dim <= 0 || max_blocks < 0 || n_kv_heads <= 0 || max_kv_len < 0) return 0;
+  auto a16 = [](size_t v) { return (v + 15) / 16 * 16; };
+  (void)decode_num_splits(1, 4, 4, 32);  // reads the switch once
+  int64_t by_len = (max_kv_len + 31) / 32 / 8;
+  by_len = by_len < 1 ? 1 : (by_len > 32 ? 32 : by_len);
+  int64_t suffix_rows = batch * by_len;
+  const int64_t by_grid = (1024 + n_kv_heads - 1) / n_kv_heads + batch;
+  suffix_rows = suffix_rows < by_grid ? suffix_rows : by_grid;
+  if (g_split_override > 0) suffix_rows = batch * (g_split_override > 32 ? 32 : g_split_override);
+  const size_t row = (size_t)n_q_heads * (head_dim + 2) * sizeof(float);
+  return a16((size_t)(2 * batch + batch * max_blocks) * sizeof(int32_t)) + a16((size_t)suffix_rows * row) +
+         a16((size_t)batch * 8 * row);
+}
+
+int xllm_mi355_shared_prefix_decode_plan(int64_t batch, int64_t n_q_heads, int64_t n_kv_heads, int64_t block_size,
+                                         int64_t max_prefix_blocks, int64_t max_kv_len, int32_t* rows_per_tile,
+                                         int32_t* prefix_splits, int32_t* suffix_hpw, int32_t* suffix_nsplit) {
+  if (batch <= 0 || n_q_heads <= 0 || n_kv_heads <= 0 || n_q_heads % n_kv_heads || block_size <= 0 || max_prefix_blocks < 0 ||
+      max_kv_len < 0)
+    return XM_ERR_INVALID;
+  const int h = decode_heads_per_wg(batch, n_kv_heads);
+  if (rows_per_tile) *rows_per_tile = shared_prefix_rows_per_tile();
+  if (prefix_splits) *prefix_splits = shared_prefix_num_splits(batch, n_q_heads, n_kv_heads, block_size, max_prefix_blocks);
+  if (suffix_hpw) *suffix_hpw = h;
+  if (suffix_nsplit) *suffix_nsplit = decode_num_splits(batch, n_kv_heads, h, max_kv_len);
+  return XM_OK;
+}
+
+int xllm_mi355_paged_decode_attention_shared_prefix(const void* q, const void* k_cache, const void* v_cache, void* out,
+                                                    const int32_t* kv_lens, const int32_t* block_table, int64_t max_blocks,
+                                                    const int32_t* group_cu, const int32_t* group_prefix_blocks, int64_t n_groups,
+                                                    int64_t batch, int64_t n_q_heads, int64_t n_kv_heads, int64_t head_dim,
+                                                    int64_t block_size, int64_t n_blocks, int64_t q_stride, int64_t max_kv_len,
+                                                    int64_t max_prefix_blocks, float scale, int prefix_splits, int dtype,
+                                                    void* workspace, size_t workspace_bytes, void* stream) {
+  (void)n_blocks;
+  if (!q || !k_cache || !v_cache || !out || !kv_lens || !block_table || !group_cu || !group_prefix_blocks || !workspace)
+    return XM_ERR_INVALID;
+  if (batch < 0 || n_groups < 1 || n_q_heads <= 0 || n_kv_heads <= 0 || n_q_heads % n_kv_heads || block_size <= 0 ||
+      max_blocks <= 0 || max_prefix_blocks < 0 || max_prefix_blocks > max_blocks || max_kv_len < 0 || prefix_splits < 0)
+    return XM_ERR_INVALID;
+  if ((head_dim != 64 && head_dim != 128) || n_q_heads / n_kv_heads > 16 || (dtype != XM_BF16 && dtype != XM_F16))
+    return XM_ERR_UNSUPPORTED;
+  if ((uintptr_t)q % 16 || (uintptr_t)k_cache % 16 || (uintptr_t)v_cache % 16 || (uintptr_t)workspace % 16 || q_stride % 8)
+    return XM_ERR_UNSUPPORTED;
+  if (workspace_bytes < xllm_mi355_shared_prefix_decode_workspace_bytes(batch, n_q_heads, head_dim, max_blocks, max_kv_len, n_kv_heads))
+    return XM_ERR_WORKSPACE;
+  if (batch == 0) return XM_OK;
+  const int hpw = decode_heads_per_wg(batch, n_kv_heads);
+  const int suffix_nsplit = decode_num_splits(batch, n_kv_heads, hpw, max_kv_len);
+  int psplit = prefix_splits > 0 ? prefix_splits : shared_prefix_num_splits(batch, n_q_heads, n_kv_heads, block_size, max_prefix_blocks);
+  psplit = psplit > 8 ? 8 : psplit;
+  hipStream_t s = (hipStream_t)stream;
+#define XM_SHARED(T, DD)                                                                                                    \
+  return launch_shared_prefix_decode<T, DD>(q, k_cache, v_cache, out, kv_lens, block_table, max_blocks, group_cu,           \
+                                            group_prefix_blocks, n_groups, batch, n_q_heads, n_kv_heads, block_size, q_stride, \
+                                            scale, hpw, suffix_nsplit, psplit, workspace, s)
+  if (dtype == XM_BF16 && head_dim == 128) XM_SHARED(bf16_t, 128);
+  if (dtype == XM_BF16 && head_dim == 64) XM_SHARED(bf16_t, 64);
+  if (dtype == XM_F16 && head_dim == 128) XM_SHARED(f16_t, 128);
+  if (dtype == XM_F16 && head_dim == 64) XM_SHARED(f16_t, 64);
+#undef XM_SHARED
   return XM_ERR_UNSUPPORTED;
 }
 

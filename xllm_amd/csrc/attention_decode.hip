@@ -21,45 +21,9 @@
 //  * tile t+1 (16 KiB of K+V per wave) is in flight in registers while tile t is computed:
 //    8 waves/CU x 16-32 KiB = 128-256 KiB outstanding per CU.
 #include "common.h"
+#include "attention_traits.h"
 
 namespace xm {
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-template <typename T>
-struct AttnTraits;
-template <>
-struct AttnTraits<bf16_t> {
-  using x8 = bf16x8_t;
-  using x4 = bf16x4_t;
-  using elem = __bf16;
-  static __device__ __forceinline__ f32x4_t mfma(x8 a, x8 b, f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ x4 tr_read(const void* lds_ptr) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) x4*)lds_ptr);
-  }
-};
-template <>
-struct AttnTraits<f16_t> {
-  using x8 = f16x8_t;
-  using x4 = f16x4_t;
-  using elem = _Float16;
-  static __device__ __forceinline__ f32x4_t mfma(x8 a, x8 b, f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ x4 tr_read(const void* lds_ptr) {
-    typedef __fp16 hfp16x4 __attribute__((__vector_size__(8)));
-    hfp16x4 r = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) hfp16x4*)lds_ptr);
-    x4 o;
-    __builtin_memcpy(&o, &r, 8);
-    return o;
-  }
-};
 
 constexpr int kTile = 32;         // tokens per tile (= K dim of the PV MFMA)
 constexpr float kNegBig = -1e30f;  // finite "-inf" for the running max (log2 domain)
@@ -695,6 +659,43 @@ int launch_paged_decode(const void* q, const void* kc, const void* vc, void* out
   }
   return hip_check_launch();
 }
+
+// the suffix stage of shared-prefix decode (attention_shared_prefix.hip): the same kernel on the caller's plan (hpw, nsplit), always
+// in part_mode -- (o, m, l) of every (sequence, head, split) at [(b * nq + head) * nsplit + split], log2 domain -- no window, no
+// output row. A sequence of 0 tokens leaves (0, -1e30, 0).
+template <typename T, int D>
+int launch_paged_decode_partials(const void* q, const void* kc, const void* vc, float* part_o, float* part_ml,
+                                 const int32_t* kv_lens, const int32_t* block_table, int64_t max_blocks, int64_t batch, int64_t nq,
+                                 int64_t nkv, int64_t block_size, int64_t q_stride, float scale, int nsplit, int hpw, hipStream_t s) {
+  const float scale_log2 = scale * 1.4426950408889634f;
+  const dim3 grid((unsigned)(batch * (nkv / hpw) * nsplit));
+  const int wide_store = (uintptr_t)part_o % 16 == 0;
+  const bool krows = hpw < nkv;
+#define XM_DECODE_PART(UNI_, KROWS_)                                                                                          \
+  hipLaunchKernelGGL((paged_decode_kernel<T, D, UNI_, false, KROWS_>), grid, dim3(256), 0, s, (const T*)q, (const T*)kc,      \
+                     (const T*)vc, (T*)nullptr, part_o, part_ml, (const int32_t*)nullptr, kv_lens, block_table, (int)max_blocks, \
+                     (int)nq, (int)nkv, (int)block_size, q_stride, scale_log2, nsplit, hpw, -1, (int8_t*)nullptr,              \
+                     (float*)nullptr, 1, wide_store)
+  if (block_size % kTile == 0) {
+    if (krows) XM_DECODE_PART(true, true);
+    else XM_DECODE_PART(true, false);
+  } else {
+    if (krows) XM_DECODE_PART(false, true);
+    else XM_DECODE_PART(false, false);
+  }
+#undef XM_DECODE_PART
+  return hip_check_launch();
+}
+
+#define XM_DECODE_PART_INST(T, D)                                                                                         \
+  template int launch_paged_decode_partials<T, D>(const void*, const void*, const void*, float*, float*, const int32_t*, \
+                                                  const int32_t*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,   \
+                                                  float, int, int, hipStream_t)
+XM_DECODE_PART_INST(bf16_t, 128);
+XM_DECODE_PART_INST(bf16_t, 64);
+XM_DECODE_PART_INST(f16_t, 128);
+XM_DECODE_PART_INST(f16_t, 64);
+#undef XM_DECODE_PART_INST
 
 template int launch_paged_decode<bf16_t, 128>(const void*, const void*, const void*, void*, const int32_t*,
                                               const int32_t*, const int32_t*, int64_t, int64_t, int64_t, int64_t,

@@ -11,6 +11,7 @@
 #include <string.h>
 
 #include "../../include/xllm_mi355.h"
+#include "xllm_mi355_shared_prefix.h"
 
 extern "C" int xllm_mi355_host_cache_slots(const int32_t* block_ids, int64_t n_blocks, int64_t block_size,
                                            int64_t pos_start, int64_t pos_end, int32_t* slots) {
@@ -78,6 +79,52 @@ extern "C" int xllm_mi355_host_build_batch(const int32_t* n_kv_cache_tokens, con
   out->q_max_seq_len = q_max;
   out->kv_max_seq_len = kv_max;
   out->total_kv_len = kv_cu;
+  return XM_OK;
+}
+
+// ---- groups of sequences whose block-table rows start with the same pages (the argument of the shared-prefix decode operator):
+// runs in batch order, see xllm_mi355_shared_prefix.h for the rule
+extern "C" int xllm_mi355_host_shared_prefix_groups(const int32_t* block_table, int64_t max_blocks, const int32_t* kv_lens,
+                                                    int64_t batch, int64_t block_size, int64_t min_group,
+                                                    int64_t min_prefix_blocks, int32_t* group_cu, int32_t* group_prefix_blocks,
+                                                    int32_t* n_groups) {
+  if (!n_groups || !group_cu || !group_prefix_blocks || batch < 0 || block_size <= 0 || max_blocks < 0) return XM_ERR_INVALID;
+  if (batch > 0 && (!block_table || !kv_lens)) return XM_ERR_INVALID;
+  for (int64_t b = 0; b < batch; ++b)
+    if (kv_lens[b] < 0) return XM_ERR_INVALID;
+  auto full_pages = [&](int64_t b) {
+    const int64_t c = kv_lens[b] / block_size;
+    return c < max_blocks ? c : max_blocks;
+  };
+  int32_t ng = 0;
+  group_cu[0] = 0;
+  auto close = [&](int64_t end, int64_t prefix) {
+    group_prefix_blocks[ng] = (int32_t)prefix;
+    group_cu[++ng] = (int32_t)end;
+  };
+  int64_t i = 0;
+  while (i < batch) {
+    if (kv_lens[i] == 0) {
+      close(++i, 0);
+      continue;
+    }
+    int64_t c = full_pages(i), j = i + 1;
+    const int32_t* lead = block_table + i * max_blocks;
+    for (; j < batch && kv_lens[j] != 0; ++j) {
+      int64_t cj = full_pages(j);
+      cj = cj < c ? cj : c;
+      const int32_t* row = block_table + j * max_blocks;
+      int64_t common = 0;
+      while (common < cj && row[common] == lead[common]) ++common;
+      if (common < min_prefix_blocks) break;
+      c = common;
+    }
+    if (j - i >= min_group && c >= min_prefix_blocks) close(j, c);
+    else
+      for (int64_t b = i; b < j; ++b) close(b + 1, 0);
+    i = j;
+  }
+  *n_groups = ng;
   return XM_OK;
 }
 

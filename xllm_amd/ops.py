@@ -768,6 +768,41 @@ def paged_attention(q, k_cache, v_cache, cu_seqlens_q, kv_seq_lens, block_table,
     return o
 
 
+def shared_prefix_decode_plan(batch: int, n_q_heads: int, n_kv_heads: int, block_size: int, max_prefix_blocks: int,
+                              max_kv_len: int):
+    """xllm_mi355_shared_prefix_decode_plan: (rows_per_tile, prefix_splits, suffix_hpw, suffix_nsplit) that
+    paged_attention_shared_prefix takes for these scalars (read-only, no launch)."""
+    v = [C.c_int32(-1) for _ in range(4)]
+    check(_lib.lib().xllm_mi355_shared_prefix_decode_plan(batch, n_q_heads, n_kv_heads, block_size, max_prefix_blocks, max_kv_len,
+                                                          *[C.addressof(x) for x in v]), "shared_prefix_decode_plan")
+    return tuple(x.value for x in v)
+
+
+def paged_attention_shared_prefix(q, k_cache, v_cache, kv_seq_lens, block_table, group_cu, group_prefix_blocks, max_kv_len,
+                                  max_prefix_blocks, scale, prefix_splits=0, out=None):
+    """Decode attention for a batch whose contiguous groups of sequences share the leading pages of their block-table rows
+    (xllm_mi355_paged_decode_attention_shared_prefix; attention.shared_prefix_groups builds the two group tensors). The result is
+    that of paged_attention(q, ..., max_q_len=1) on the same tensors: q [B, nq, d], caches [n_blocks, bs, nkv, d], group_cu int32
+    [n_groups + 1], group_prefix_blocks int32 [n_groups], all on the device -> out [B, nq * d]."""
+    _need_cuda(q, k_cache, v_cache, kv_seq_lens, block_table, group_cu, group_prefix_blocks)
+    B, nq, d = q.shape
+    n_blocks, bs, nkv, _ = k_cache.shape
+    if kv_seq_lens.numel() != B or group_cu.dtype != torch.int32 or group_prefix_blocks.dtype != torch.int32 or \
+            group_cu.numel() != group_prefix_blocks.numel() + 1 or not group_cu.is_contiguous() or \
+            not group_prefix_blocks.is_contiguous():
+        raise Mi355Error("paged_attention_shared_prefix: one query token per sequence; group_cu int32 [n_groups + 1], "
+                         "group_prefix_blocks int32 [n_groups], contiguous")
+    o = out if out is not None else torch.empty(B, nq * d, dtype=q.dtype, device=q.device)
+    bt = block_table if block_table.is_contiguous() else block_table.contiguous()
+    need = _lib.lib().xllm_mi355_shared_prefix_decode_workspace_bytes(B, nq, d, bt.size(1), max_kv_len, nkv)
+    ws = _attn_workspace(q.device, need)
+    check(_lib.lib().xllm_mi355_paged_decode_attention_shared_prefix(
+        _p(q), _p(k_cache), _p(v_cache), _p(o), _p(kv_seq_lens), _p(bt), bt.size(1), _p(group_cu), _p(group_prefix_blocks),
+        group_prefix_blocks.numel(), B, nq, nkv, d, bs, n_blocks, q.stride(0), max_kv_len, max_prefix_blocks, scale,
+        prefix_splits, _dt(q), _p(ws), ws.numel(), _stream()), "paged_attention_shared_prefix")
+    return o
+
+
 def mla_decode(q, k_cache, seqlens_k, block_table, head_size_v: int, scale: float, max_kv_len: int, out=None):
     """flash_mla::dense_decode argument set (kernels/dcu/flash_mla_adapter.h:40-50): q [B, H, 576] =
     [q_nope*W_kc || q_pe], k_cache [n_blocks, block, 1, 576]; returns [B, H, head_size_v]."""
