@@ -38,12 +38,18 @@ def test_gemm_parity_under_kernel_selector(env):
     {"XLLM_MI355_MLA_PREFILL": "0"},                         # prefill: one decode-kernel entry per query token
     {"XLLM_MI355_MLA_PREFILL": "1"},                         # prefill: the tile-sharing kernel on every batch size
     {"XLLM_MI355_MLA_PREFILL": "1", "XLLM_MI355_MLA_PREFILL_P": "2"},   # ... with P = hi + lo (fp32-P accuracy)
+    {"XLLM_MI355_MLA_SPLITS": "7"},                          # the uneven merge above four splits
+    {"XLLM_MI355_MLA_SPLITS": "32"},                         # the largest count the workspace is sized for
 ], ids=["mla_dma_split3", "mla_dma_nosplit", "mla_prefill_per_token",
-        "mla_prefill_shared_forced", "mla_prefill_shared_p_hi_lo"])
+        "mla_prefill_shared_forced", "mla_prefill_shared_p_hi_lo", "mla_dma_split7", "mla_dma_split32"])
 def test_mla_parity_under_kernel_selector(env):
+    """The MLA tests of test_gpu_parity.py and every arm, length edge and rescale case of tests/test_gpu_mla_arms.py (`-k mla`
+    selects that whole file) under each MLA selector. The latter asserts through xllm_mi355_mla_plan what each switch dictates: min(n, 32, what the workspace holds) splits, the tile-sharing
+    arm for the small per-token calls under XLLM_MI355_MLA_PREFILL=1"""
     e = dict(os.environ)
     e.update(env)
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_parity.py"), "-q", "-x",
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_parity.py"),
+                        os.path.join(ROOT, "tests", "test_gpu_mla_arms.py"), "-q", "-x",
                         "-k", "mla", "-p", "no:cacheprovider"], cwd=ROOT, env=e, capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]

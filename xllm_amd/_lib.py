@@ -118,6 +118,7 @@ _SIGS = {
                                     i64, f32, ci, i64, ci, vp, sz, vp], ci),
     "xllm_mi355_shared_prefix_decode_workspace_bytes": ([i64, i64, i64, i64, i64, i64], sz),
     "xllm_mi355_shared_prefix_decode_plan": ([i64, i64, i64, i64, i64, i64, vp, vp, vp, vp], ci),
+    "xllm_mi355_mla_plan": ([i64, i64, i64, i64, i64, sz, vp, vp], ci),
     "xllm_mi355_paged_decode_attention_shared_prefix": ([vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, i64, i64, i64, i64, i64, i64,
                                                          i64, i64, i64, f32, ci, ci, vp, sz, vp], ci),
 }

@@ -15,6 +15,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "xllm_mi355_mla_plan.h"
 
 namespace xm {
 
@@ -863,10 +864,29 @@ __global__ __launch_bounds__(256) void mla_expand_queries_kernel(const int32_t* 
   }
 }
 
-static int launch_mla(const void* q, const void* k_cache, void* out, const int32_t* seqlens_k, const int32_t* q_seq,
-                      const int32_t* q_kvlen, const int32_t* block_table, int64_t max_blocks, int64_t entries,
-                      int64_t n_heads, int64_t block_size, int64_t max_kv_len, float scale, int dtype, void* workspace,
-                      size_t workspace_bytes, hipStream_t s) {
+// ---- the launch plan. ONE function decides which kernel a call takes and how many split-KV slices it runs; the two launchers
+// below and the read-only query xllm_mi355_mla_plan (xllm_mi355_mla_plan.h) call it, so a test can name the arm its shape takes.
+// The three product switches are read once per process, here and nowhere else.
+enum MlaArm {
+  kMlaArmStaged = 0,     // mla_decode_kernel<T, false>: page not a multiple of 64 (and the tuning flavour's register-staged A/B arm)
+  kMlaArmDma = 1,        // mla_decode_dma_kernel<T, false>
+  kMlaArmDmaNt = 2,      // mla_decode_dma_kernel<T, true>: decode, one head block
+  kMlaArmShareP1 = 3,    // mla_prefill_dma_kernel<T, true>: one rounded P
+  kMlaArmShareHiLo = 4,  // mla_prefill_dma_kernel<T, false>: P = hi + lo
+};
+struct MlaPlan {
+  int arm;
+  int64_t nsplit;  // after degradation to the workspace; 1 for the tile-sharing arms
+};
+
+static size_t mla_prefill_idx_bytes(int64_t total_q_tokens) {
+  return (((size_t)total_q_tokens * 2 * sizeof(int32_t)) + 255) & ~(size_t)255;
+}
+
+// decode form: one entry per sequence (per_token = false) or per query token (per-token prefill, per_token = true);
+// workspace_bytes is what the (o, m, l) partials may use
+static MlaPlan mla_plan_entries(int64_t entries, bool per_token, int64_t n_heads, int64_t block_size, int64_t max_kv_len,
+                                size_t workspace_bytes) {
   const int64_t hblocks = (n_heads + 15) / 16;
   const int64_t tiles = (max_kv_len + kMlaTile - 1) / kMlaTile;
   // XLLM_MI355_MLA_SPLITS (product switch, read once): force the split-KV count (the parity tests cover the counts the planner
@@ -883,19 +903,47 @@ static int launch_mla(const void* q, const void* k_cache, void* out, const int32
   if (nsplit < 1) nsplit = 1;
   if (nsplit > 32) nsplit = 32;
   const size_t per_split = (size_t)entries * n_heads * (kMlaDV + 2) * sizeof(float);
-  if (!workspace) workspace_bytes = 0;
   if ((size_t)nsplit * per_split > workspace_bytes) nsplit = (int64_t)(workspace_bytes / per_split);
   if (nsplit < 1) nsplit = 1;
+  // every latent byte is read once (decode, one head block): non-temporal DMA
+  return MlaPlan{dma ? (hblocks == 1 && !per_token ? kMlaArmDmaNt : kMlaArmDma) : kMlaArmStaged, nsplit};
+}
+
+// total_q_tokens = 0: xllm_mi355_mla_decode on `batch` sequences; otherwise xllm_mi355_mla_prefill, whose workspace starts with
+// the per-token index arrays (the caller has checked that they fit)
+static MlaPlan mla_plan(int64_t batch, int64_t total_q_tokens, int64_t n_heads, int64_t block_size, int64_t max_kv_len,
+                        size_t workspace_bytes) {
+  if (total_q_tokens == 0) return mla_plan_entries(batch, false, n_heads, block_size, max_kv_len, workspace_bytes);
+  // enough query tokens to fill the chip without a split-KV: the kernel that shares every KV tile between four tokens
+  // (XLLM_MI355_MLA_PREFILL = 0: never, 1: whenever the page size allows it; default: by workgroup count)
+  static int share_mode = -2;
+  if (share_mode == -2) share_mode = xm_switch("XLLM_MI355_MLA_PREFILL", -1);
+  const int64_t n_groups = (total_q_tokens + 3) / 4, hblocks = (n_heads + 15) / 16;
+  if (block_size % kMlaTile == 0 && share_mode != 0 && (share_mode == 1 || n_groups * hblocks >= 128)) {
+    static int p_mode = -2;   // XLLM_MI355_MLA_PREFILL_P=2: P = hi + lo (fp32-P accuracy), product switch
+    if (p_mode == -2) p_mode = xm_switch("XLLM_MI355_MLA_PREFILL_P", 1);
+    return MlaPlan{p_mode == 2 ? kMlaArmShareHiLo : kMlaArmShareP1, 1};
+  }
+  return mla_plan_entries(total_q_tokens, true, n_heads, block_size, max_kv_len,
+                          workspace_bytes - mla_prefill_idx_bytes(total_q_tokens));
+}
+
+static int launch_mla(const void* q, const void* k_cache, void* out, const int32_t* seqlens_k, const int32_t* q_seq,
+                      const int32_t* q_kvlen, const int32_t* block_table, int64_t max_blocks, int64_t entries,
+                      int64_t n_heads, int64_t block_size, float scale, int dtype, void* workspace, const MlaPlan& plan,
+                      hipStream_t s) {
+  const int64_t hblocks = (n_heads + 15) / 16;
+  const int64_t nsplit = plan.nsplit;
   float* part_o = reinterpret_cast<float*>(workspace);
   float* part_ml = part_o ? part_o + (size_t)entries * n_heads * nsplit * kMlaDV : nullptr;
   const float scale_log2 = scale * 1.4426950408889634f;
   const dim3 grid((unsigned)(entries * hblocks * nsplit));
   XM_DISPATCH_HALF(dtype, T, {
-    if (dma && hblocks == 1 && !q_seq)   // every latent byte is read once: non-temporal DMA
+    if (plan.arm == kMlaArmDmaNt)
       hipLaunchKernelGGL((mla_decode_dma_kernel<T, true>), grid, dim3(256), 0, s, (const T*)q, (const T*)k_cache, (T*)out,
                          part_o, part_ml, seqlens_k, block_table, (int)max_blocks, (int)n_heads, (int)block_size,
                          scale_log2, (int)nsplit, q_seq, q_kvlen);
-    else if (dma)
+    else if (plan.arm == kMlaArmDma)
       hipLaunchKernelGGL((mla_decode_dma_kernel<T, false>), grid, dim3(256), 0, s, (const T*)q, (const T*)k_cache, (T*)out,
                          part_o, part_ml, seqlens_k, block_table, (int)max_blocks, (int)n_heads, (int)block_size,
                          scale_log2, (int)nsplit, q_seq, q_kvlen);
@@ -931,8 +979,10 @@ extern "C" int xllm_mi355_mla_decode(const void* q, const void* k_cache, void* o
   if (head_dim != kMlaD || head_dim_v != kMlaDV) return XM_ERR_UNSUPPORTED;
   if ((uintptr_t)q % 16 || (uintptr_t)k_cache % 16) return XM_ERR_UNSUPPORTED;
   if (batch == 0) return XM_OK;
-  return launch_mla(q, k_cache, out, seqlens_k, nullptr, nullptr, block_table, max_blocks, batch, n_heads, block_size,
-                    max_kv_len, scale, dtype, workspace, workspace_bytes, (hipStream_t)stream);
+  if (!workspace) workspace_bytes = 0;
+  const MlaPlan plan = mla_plan(batch, 0, n_heads, block_size, max_kv_len, workspace_bytes);
+  return launch_mla(q, k_cache, out, seqlens_k, nullptr, nullptr, block_table, max_blocks, batch, n_heads, block_size, scale,
+                    dtype, workspace, plan, (hipStream_t)stream);
 }
 
 extern "C" int xllm_mi355_mla_prefill(const void* q, const void* k_cache, void* out, const int32_t* cu_q,
@@ -948,23 +998,18 @@ extern "C" int xllm_mi355_mla_prefill(const void* q, const void* k_cache, void* 
   if (head_dim != kMlaD || head_dim_v != kMlaDV) return XM_ERR_UNSUPPORTED;
   if ((uintptr_t)q % 16 || (uintptr_t)k_cache % 16) return XM_ERR_UNSUPPORTED;
   if (batch == 0 || total_q_tokens == 0) return XM_OK;
-  const size_t idx_bytes = (((size_t)total_q_tokens * 2 * sizeof(int32_t)) + 255) & ~(size_t)255;
+  const size_t idx_bytes = mla_prefill_idx_bytes(total_q_tokens);
   if (!workspace || workspace_bytes < idx_bytes) return XM_ERR_WORKSPACE;
   int32_t* q_seq = reinterpret_cast<int32_t*>(workspace);
   int32_t* q_kvlen = q_seq + total_q_tokens;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(mla_expand_queries_kernel, dim3((unsigned)batch), dim3(256), 0, s, cu_q, kv_lens, causal, q_seq,
                      q_kvlen);
-  // enough query tokens to fill the chip without a split-KV: the kernel that shares every KV tile between four tokens
-  // (XLLM_MI355_MLA_PREFILL = 0: never, 1: whenever the page size allows it; default: by workgroup count)
-  static int share_mode = -2;
-  if (share_mode == -2) share_mode = xm_switch("XLLM_MI355_MLA_PREFILL", -1);
-  const int64_t n_groups = (total_q_tokens + 3) / 4, hblocks = (n_heads + 15) / 16;
-  if (block_size % kMlaTile == 0 && share_mode != 0 && (share_mode == 1 || n_groups * hblocks >= 128)) {
+  const MlaPlan plan = mla_plan(batch, total_q_tokens, n_heads, block_size, max_kv_len, workspace_bytes);
+  if (plan.arm == kMlaArmShareP1 || plan.arm == kMlaArmShareHiLo) {
+    const int64_t n_groups = (total_q_tokens + 3) / 4, hblocks = (n_heads + 15) / 16;
     const dim3 grid((unsigned)(((n_groups + 7) / 8) * 8 * hblocks));
-    static int p_mode = -2;   // XLLM_MI355_MLA_PREFILL_P=2: P = hi + lo (fp32-P accuracy), product switch
-    if (p_mode == -2) p_mode = xm_switch("XLLM_MI355_MLA_PREFILL_P", 1);
-    if (p_mode == 2) {
+    if (plan.arm == kMlaArmShareHiLo) {
       XM_DISPATCH_HALF(dtype, T, {
         hipLaunchKernelGGL((mla_prefill_dma_kernel<T, false>), grid, dim3(256), 0, s, (const T*)q, (const T*)k_cache,
                            (T*)out, block_table, (int)max_blocks, (int)n_heads, (int)block_size,
@@ -980,6 +1025,15 @@ extern "C" int xllm_mi355_mla_prefill(const void* q, const void* k_cache, void* 
     return hip_check_launch();
   }
   return launch_mla(q, k_cache, out, kv_lens, q_seq, q_kvlen, block_table, max_blocks, total_q_tokens, n_heads,
-                    block_size, max_kv_len, scale, dtype, reinterpret_cast<uint8_t*>(workspace) + idx_bytes,
-                    workspace_bytes - idx_bytes, s);
+                    block_size, scale, dtype, reinterpret_cast<uint8_t*>(workspace) + idx_bytes, plan, s);
+}
+
+extern "C" int xllm_mi355_mla_plan(int64_t batch, int64_t total_q_tokens, int64_t n_heads, int64_t block_size,
+                                   int64_t max_kv_len, size_t workspace_bytes, int32_t* arm, int32_t* nsplit) {
+  if (batch <= 0 || total_q_tokens < 0 || n_heads <= 0 || block_size <= 0 || max_kv_len < 0) return XM_ERR_INVALID;
+  if (total_q_tokens > 0 && workspace_bytes < mla_prefill_idx_bytes(total_q_tokens)) return XM_ERR_WORKSPACE;
+  const MlaPlan plan = mla_plan(batch, total_q_tokens, n_heads, block_size, max_kv_len, workspace_bytes);
+  if (arm) *arm = plan.arm;
+  if (nsplit) *nsplit = (int32_t)plan.nsplit;
+  return XM_OK;
 }
