@@ -121,6 +121,10 @@ _SIGS = {
     "xllm_mi355_mla_plan": ([i64, i64, i64, i64, i64, sz, vp, vp], ci),
     "xllm_mi355_paged_decode_attention_shared_prefix": ([vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, i64, i64, i64, i64, i64, i64,
                                                          i64, i64, i64, f32, ci, ci, vp, sz, vp], ci),
+    # csrc/xllm_mi355_fp8_static.h
+    "xllm_mi355_act_and_mul_static_fp8_quant": ([vp, vp, vp, i64, i64, ci, ci, vp], ci),
+    "xllm_mi355_paged_decode_attention_fp8": ([vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, i64, i64,
+                                               f32, i64, ci, vp, sz, vp], ci),
 }
 # entry points declared in the header but implemented in a later build step are bound lazily
 _OPTIONAL = {

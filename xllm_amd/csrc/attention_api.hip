@@ -3,6 +3,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "xllm_mi355_fp8_static.h"
 #include "xllm_mi355_shared_prefix.h"
 
 namespace xm {
@@ -13,6 +14,11 @@ int launch_paged_decode(const void* q, const void* kc, const void* vc, void* out
                         int64_t nq, int64_t nkv, int64_t block_size, int64_t q_stride, int64_t max_kv_len,
                         float scale, int64_t window_left, void* workspace, size_t ws_bytes, hipStream_t s,
                         int8_t* out_q, float* out_scale);
+template <typename T, int D>
+int launch_paged_decode_fp8(const void* q, const void* kc, const void* vc, void* out, uint8_t* out_f8, const float* f8_scale,
+                            const int32_t* kv_lens, const int32_t* block_table, int64_t max_blocks, int64_t batch, int64_t nq,
+                            int64_t nkv, int64_t block_size, int64_t q_stride, int64_t max_kv_len, float scale,
+                            int64_t window_left, void* workspace, size_t ws_bytes, hipStream_t s);
 
 // attention_shared_prefix.hip
 template <typename T, int D>
@@ -199,6 +205,35 @@ int xllm_mi355_paged_decode_attention_int8_ws(const void* q, const void* k_cache
   if (dtype == XM_F16 && head_dim == 128) XM_DECODEQ(f16_t, 128);
   if (dtype == XM_F16 && head_dim == 64) XM_DECODEQ(f16_t, 64);
 #undef XM_DECODEQ
+  return XM_ERR_UNSUPPORTED;
+}
+
+// ---- static-scale fp8 decode (xllm_mi355_fp8_static.h): the decode form of xllm_mi355_paged_attention with the e4m3 operand of
+// o_proj written by the attention epilogue (one grid split) or by the merge launch (split-KV)
+int xllm_mi355_paged_decode_attention_fp8(const void* q, const void* k_cache, const void* v_cache, void* out, uint8_t* out_q,
+                                          const float* out_scale, const int32_t* kv_lens, const int32_t* block_table,
+                                          int64_t max_blocks, int64_t batch, int64_t n_q_heads, int64_t n_kv_heads,
+                                          int64_t head_dim, int64_t block_size, int64_t n_blocks, int64_t q_stride,
+                                          int64_t max_kv_len, float scale, int64_t window_left, int dtype, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+  (void)n_blocks;
+  if (!q || !k_cache || !v_cache || !out_q || !out_scale || !kv_lens || !block_table) return XM_ERR_INVALID;
+  if (batch < 0 || n_q_heads <= 0 || n_kv_heads <= 0 || n_q_heads % n_kv_heads || block_size <= 0 || max_blocks <= 0)
+    return XM_ERR_INVALID;
+  if ((head_dim != 64 && head_dim != 128) || n_q_heads / n_kv_heads > 16 || (dtype != XM_BF16 && dtype != XM_F16))
+    return XM_ERR_UNSUPPORTED;
+  if ((uintptr_t)q % 16 || (uintptr_t)k_cache % 16 || (uintptr_t)v_cache % 16 || q_stride % 8) return XM_ERR_UNSUPPORTED;
+  if (batch == 0) return XM_OK;
+  hipStream_t s = (hipStream_t)stream;
+#define XM_DECODE8(T, DD)                                                                                                  \
+  return launch_paged_decode_fp8<T, DD>(q, k_cache, v_cache, out, out_q, out_scale, kv_lens, block_table, max_blocks, batch, \
+                                        n_q_heads, n_kv_heads, block_size, q_stride, max_kv_len, scale, window_left,       \
+                                        workspace, workspace ? workspace_bytes : 0, s)
+  if (dtype == XM_BF16 && head_dim == 128) XM_DECODE8(bf16_t, 128);
+  if (dtype == XM_BF16 && head_dim == 64) XM_DECODE8(bf16_t, 64);
+  if (dtype == XM_F16 && head_dim == 128) XM_DECODE8(f16_t, 128);
+  if (dtype == XM_F16 && head_dim == 64) XM_DECODE8(f16_t, 64);
+#undef XM_DECODE8
   return XM_ERR_UNSUPPORTED;
 }
 

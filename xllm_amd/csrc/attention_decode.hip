@@ -30,7 +30,12 @@ constexpr float kNegBig = -1e30f;  // finite "-inf" for the running max (log2 do
 
 // D = head dim (K and V), UNIFORM: block_size % 32 == 0 so a tile lives in one page
 // KROWS: how the K tile is fetched (see issue_loads) -- chosen by the launch plan, bit-identical results either way
-template <typename T, int D, bool UNIFORM, bool DEEP, bool KROWS>
+// F8: the static-scale fp8 form (xllm_mi355_fp8_static.h) -- out_q takes e4m3 bytes and out_scale is READ: out_scale[0] is the
+// static per-tensor scale. The one-pass epilogue stores the quantisation of the 8 values of a work item beside the 16-bit store;
+// element-wise, so every plan with one grid split takes it, whatever hpw, and there is no second pass. wide_store then carries two
+// flags (bit 0: 16-byte stores of out, bit 1: 8-byte stores of out_q). A template parameter, not a run-time branch, with the
+// argument list unchanged: the F8 = false instantiations compile from code without it (profiles/fp8_static_decode.txt).
+template <typename T, int D, bool UNIFORM, bool DEEP, bool KROWS, bool F8 = false>
 __global__ __launch_bounds__(256, DEEP ? 1 : 2) void paged_decode_kernel(
     const T* __restrict__ q, const T* __restrict__ kc, const T* __restrict__ vc, T* __restrict__ out,
     float* __restrict__ part_o, float* __restrict__ part_ml, const int32_t* __restrict__ cu_q,
@@ -352,6 +357,13 @@ __global__ __launch_bounds__(256, DEEP ? 1 : 2) void paged_decode_kernel(
   __shared__ float red[32];
   float val[4][8];  // int8 form: the rounded values wait here for the row maximum
   float amax = 0.0f;
+  float f8_sinv = 0.0f;
+  bool wide_f8 = false;
+  if constexpr (F8) {
+    f8_sinv = 1.0f / out_scale[0];   // fp8_quant_kernel's reciprocal (rowwise.hip)
+    wide_f8 = (wide_store & 2) != 0;
+    wide_store &= 1;
+  }
 #pragma unroll
   for (int it = 0; it < 4; ++it) {
     const int item = threadIdx.x + it * 256;
@@ -415,9 +427,27 @@ __global__ __launch_bounds__(256, DEEP ? 1 : 2) void paged_decode_kernel(
             for (int j = 0; j < 8; ++j) op16[j] = t[j];
           }
         }
+        if constexpr (F8) {  // static_scaled_fp8_quant of the 16-bit values above, from registers
+          unsigned lo = 0u, hi = 0u;
+          uint8_t f8[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            f8[j] = f32_to_e4m3_sat(val[it][j] * f8_sinv);
+            const unsigned byte = (unsigned)f8[j] << ((j & 3) * 8);
+            if (j < 4) lo |= byte;
+            else hi |= byte;
+          }
+          uint8_t* oq = reinterpret_cast<uint8_t*>(out_q) + qtok * (int64_t)nq * D + (int64_t)head * D + d;
+          if (wide_f8) *reinterpret_cast<uint2*>(oq) = make_uint2(lo, hi);
+          else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) oq[j] = f8[j];
+          }
+        }
       }
     }
   }
+  if constexpr (F8) return;
   if (!out_q) return;
   // N1 fusion: the workgroup holds ALL heads of this token (host guarantees nsplit == 1 and one head group), so the per-token
   // int8 quantisation that feeds o_proj (scaled_quantize of the 16-bit output) is done here, from the registers above.
@@ -466,6 +496,30 @@ __global__ void paged_decode_merge_kernel(const float* __restrict__ part_o, cons
   }
   const int64_t qtok = cu_q ? cu_q[b] : b;
   out[qtok * (int64_t)nq * D + (int64_t)head * D + d] = from_f32<T>(l > 0.0f ? o / l : 0.0f);
+}
+
+// the same merge, emitting the static e4m3 quantisation of the 16-bit value (and the value itself when out != NULL): merge +
+// static_scaled_fp8_quant in one launch, the expressions of both in their order. One query token per sequence.
+template <typename T, int D>
+__global__ void paged_decode_merge_fp8_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
+                                              T* __restrict__ out, uint8_t* __restrict__ out_f8,
+                                              const float* __restrict__ f8_scale, int nq, int nsplit) {
+  const int b = blockIdx.x / nq, head = blockIdx.x % nq;
+  const int d = threadIdx.x;
+  const int64_t base = ((int64_t)b * nq + head) * nsplit;
+  const float sinv = 1.0f / f8_scale[0];
+  float m_star = kNegBig;
+  for (int s = 0; s < nsplit; ++s) m_star = fmaxf(m_star, part_ml[(base + s) * 2]);
+  float o = 0.0f, l = 0.0f;
+  for (int s = 0; s < nsplit; ++s) {
+    const float f = exp2f(part_ml[(base + s) * 2] - m_star);
+    o += f * part_o[(base + s) * D + d];
+    l += f * part_ml[(base + s) * 2 + 1];
+  }
+  const T v = from_f32<T>(l > 0.0f ? o / l : 0.0f);
+  const int64_t at = (int64_t)b * nq * D + (int64_t)head * D + d;
+  if (out) out[at] = v;
+  out_f8[at] = f32_to_e4m3_sat(to_f32<T>(v) * sinv);
 }
 
 // merge + per-token int8 quantisation in one launch (N1 fusion for the plans whose workgroups do not hold a whole token:
@@ -659,6 +713,74 @@ int launch_paged_decode(const void* q, const void* kc, const void* vc, void* out
   }
   return hip_check_launch();
 }
+
+// the static-scale fp8 form (xllm_mi355_paged_decode_attention_fp8): the launch plan of launch_paged_decode -- hpw, the split
+// count and its degradation to the caller's workspace -- so that the 16-bit values quantised here are the bits paged_attention
+// writes for the same arguments. One grid split: the attention kernel's own epilogue, one launch, no workspace, for every hpw.
+// Split-KV: paged_decode_kernel in part_mode + the fp8 merge, two launches instead of three.
+template <typename T, int D>
+int launch_paged_decode_fp8(const void* q, const void* kc, const void* vc, void* out, uint8_t* out_f8, const float* f8_scale,
+                            const int32_t* kv_lens, const int32_t* block_table, int64_t max_blocks, int64_t batch, int64_t nq,
+                            int64_t nkv, int64_t block_size, int64_t q_stride, int64_t max_kv_len, float scale,
+                            int64_t window_left, void* workspace, size_t ws_bytes, hipStream_t s) {
+  const int hpw = decode_heads_per_wg(batch, nkv);
+  int nsplit = decode_num_splits(batch, nkv, hpw, max_kv_len);
+  const size_t per_split = (size_t)batch * nq * (D + 2) * sizeof(float);
+  if (!workspace) ws_bytes = 0;
+  if ((size_t)nsplit * per_split > ws_bytes) nsplit = (int)(ws_bytes / per_split);
+  if (nsplit < 1) nsplit = 1;
+  float* part_o = nsplit > 1 ? reinterpret_cast<float*>(workspace) : nullptr;
+  float* part_ml = part_o ? part_o + (size_t)batch * nq * nsplit * D : nullptr;
+  const float scale_log2 = scale * 1.4426950408889634f;
+  const dim3 grid((unsigned)(batch * (nkv / hpw) * nsplit));
+  const int wl = window_left < 0 ? -1 : (window_left > 0x3fffffff ? 0x3fffffff : (int)window_left);
+  const bool krows = hpw < nkv;
+  const bool uniform = block_size % kTile == 0;
+  if (nsplit > 1) {
+    const int wide_store = (uintptr_t)part_o % 16 == 0;
+#define XM_DECODE_PART8(UNI_, KROWS_)                                                                                          \
+  hipLaunchKernelGGL((paged_decode_kernel<T, D, UNI_, false, KROWS_>), grid, dim3(256), 0, s, (const T*)q, (const T*)kc,        \
+                     (const T*)vc, (T*)nullptr, part_o, part_ml, (const int32_t*)nullptr, kv_lens, block_table, (int)max_blocks, \
+                     (int)nq, (int)nkv, (int)block_size, q_stride, scale_log2, nsplit, hpw, wl, (int8_t*)nullptr,               \
+                     (float*)nullptr, 1, wide_store)
+    if (uniform) {
+      if (krows) XM_DECODE_PART8(true, true);
+      else XM_DECODE_PART8(true, false);
+    } else {
+      if (krows) XM_DECODE_PART8(false, true);
+      else XM_DECODE_PART8(false, false);
+    }
+#undef XM_DECODE_PART8
+    hipLaunchKernelGGL((paged_decode_merge_fp8_kernel<T, D>), dim3((unsigned)(batch * nq)), dim3(D), 0, s, part_o, part_ml,
+                       (T*)out, out_f8, f8_scale, (int)nq, nsplit);
+    return hip_check_launch();
+  }
+  const int wide_store = ((uintptr_t)out % 16 == 0 ? 1 : 0) | ((uintptr_t)out_f8 % 8 == 0 ? 2 : 0);
+#define XM_DECODE_F8(UNI_, KROWS_)                                                                                          \
+  hipLaunchKernelGGL((paged_decode_kernel<T, D, UNI_, false, KROWS_, true>), grid, dim3(256), 0, s, (const T*)q, (const T*)kc, \
+                     (const T*)vc, (T*)out, (float*)nullptr, (float*)nullptr, (const int32_t*)nullptr, kv_lens, block_table, \
+                     (int)max_blocks, (int)nq, (int)nkv, (int)block_size, q_stride, scale_log2, 1, hpw, wl,                  \
+                     reinterpret_cast<int8_t*>(out_f8), const_cast<float*>(f8_scale), 0, wide_store)
+  if (uniform) {
+    if (krows) XM_DECODE_F8(true, true);
+    else XM_DECODE_F8(true, false);
+  } else {
+    if (krows) XM_DECODE_F8(false, true);
+    else XM_DECODE_F8(false, false);
+  }
+#undef XM_DECODE_F8
+  return hip_check_launch();
+}
+
+#define XM_DECODE_F8_INST(T, D)                                                                                            \
+  template int launch_paged_decode_fp8<T, D>(const void*, const void*, const void*, void*, uint8_t*, const float*,         \
+                                             const int32_t*, const int32_t*, int64_t, int64_t, int64_t, int64_t, int64_t,  \
+                                             int64_t, int64_t, float, int64_t, void*, size_t, hipStream_t)
+XM_DECODE_F8_INST(bf16_t, 128);
+XM_DECODE_F8_INST(bf16_t, 64);
+XM_DECODE_F8_INST(f16_t, 128);
+XM_DECODE_F8_INST(f16_t, 64);
+#undef XM_DECODE_F8_INST
 
 // the suffix stage of shared-prefix decode (attention_shared_prefix.hip): the same kernel on the caller's plan (hpw, nsplit), always
 // in part_mode -- (o, m, l) of every (sequence, head, split) at [(b * nq + head) * nsplit + split], log2 domain -- no window, no

@@ -106,8 +106,9 @@ struct RowVec {
 };
 
 // gated activations (kernels/cuda/activation.cu:143-185); shared by rowwise.hip and the GEMM epilogues that fuse SiLU.mul
+// act(f) = a * b: the two factors of the last multiply, for callers that have to form the product themselves (rowwise_fp8.hip)
 template <int MODE>
-__device__ __forceinline__ float act_f(float f) {
+__device__ __forceinline__ void act_factors(float f, float& fa, float& fb) {
   // SiLU on the hardware transcendental units (v_exp_f32, v_rcp_f32) with the two cheap corrections that bring it
   // back to ~2 ulp in f32: the argument of exp2 carries its rounding residual (x*log2e in two pieces), and the
   // reciprocal takes one Newton step. 12 VALU instead of the 23 of libm expf + IEEE division, which made the fused
@@ -123,14 +124,25 @@ __device__ __forceinline__ float act_f(float f) {
     float r = __builtin_amdgcn_rcpf(dn);
     const float rn = fmaf(r, fmaf(-dn, r, 1.0f), r);
     r = (dn < 3.0e38f) ? rn : r;  // dn = inf: keep r = 0 (the Newton step would be inf * 0); NaN keeps NaN
-    return f * r;
+    fa = f;
+    fb = r;
   }
-  else if constexpr (MODE == XM_ACT_GELU) return f * 0.5f * (1.0f + erff(f * 0.70710678118654752440f));
+  else if constexpr (MODE == XM_ACT_GELU) {
+    fa = f * 0.5f;
+    fb = 1.0f + erff(f * 0.70710678118654752440f);
+  }
   else {
     const float kBeta = 1.41421356237309504880f * 1.12837916709551257390f * 0.5f;
     const float inner = kBeta * (f + 0.044715f * f * f * f);
-    return 0.5f * f * (1.0f + tanhf(inner));
+    fa = 0.5f * f;
+    fb = 1.0f + tanhf(inner);
   }
+}
+template <int MODE>
+__device__ __forceinline__ float act_f(float f) {
+  float fa, fb;
+  act_factors<MODE>(f, fa, fb);
+  return fa * fb;
 }
 
 __device__ __forceinline__ float wave_sum(float v) {

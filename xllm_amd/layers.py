@@ -75,6 +75,10 @@ class QuantLinear:
                  col_blocks=None, pack16: bool = True):
         self.mode, self.dtype, self.pg = mode, dtype, row_parallel_pg
         self.weight_packed = None
+        # mode "fp8_static": the static per-tensor activation scale a static-scale fp8 checkpoint carries for this linear
+        # (linear.cpp:130-182 input_scale), device f32 [1]; 1.0 until Qwen2Model.calibrate_fp8_static measures it
+        self.input_scale = torch.ones(1, dtype=torch.float32, device=device) if mode == "fp8_static" else None
+        self.calibrating = False
         if mode == "int8":
             # random-init weights of the architecture (N(0, initializer_range = 0.02), models/llm/qwen2.h) put through
             # the symmetric per-output-channel int8 quantisation a W8A8 checkpoint carries: w_q = round(w / s),
@@ -84,6 +88,9 @@ class QuantLinear:
             self.weight = torch.round(w / self.w_scale[:, None]).clamp_(-127, 127).to(torch.int8)
             del w
         elif mode == "fp8":
+            self.weight = (torch.randn(n, k, device=device, generator=gen)).to(torch.float8_e4m3fn)
+            self.w_scale = torch.full((1,), 1.0 / math.sqrt(k), device=device)
+        elif mode == "fp8_static":   # the weights of mode "fp8": only the activation side differs
             self.weight = (torch.randn(n, k, device=device, generator=gen)).to(torch.float8_e4m3fn)
             self.w_scale = torch.full((1,), 1.0 / math.sqrt(k), device=device)
         else:
@@ -120,6 +127,8 @@ class QuantLinear:
             self.weight_packed = ops.pack_weight_i8(self.weight)
         elif mode == "fp8" and self.weight.is_cuda:
             self.weight_packed = ops.pack_weight_fp8(self.weight)
+        elif mode == "fp8_static" and self.weight.is_cuda:
+            self.weight_packed = ops.pack_weight_fp8(self.weight)
         elif self.weight.is_cuda and self.weight.dtype in (torch.bfloat16, torch.float16) and pack16:
             self.weight_packed = ops.pack_weight_16(self.weight)     # (cfg2: BASELINE config 2 runs 16-bit linears at M = 64)
 
@@ -130,6 +139,16 @@ class QuantLinear:
             y = ops.scaled_matmul(q, self.weight, s, self.w_scale, self.dtype, self.bias, b_packed=self.weight_packed)
         elif self.mode == "fp8":
             q, s = pre_quant if pre_quant is not None else ops.fp8_scaled_quantize(x)
+            y = ops.fp8_scaled_matmul(q, self.weight, s, self.w_scale, self.dtype, self.bias, b_packed=self.weight_packed)
+        elif self.mode == "fp8_static":
+            # `pre_quant` = (e4m3, input_scale): the producer already quantised with this linear's static scale
+            if pre_quant is not None:
+                q, s = pre_quant
+            elif self.calibrating:   # calibrate_fp8_static: fp8_scaled_quantize's own amax / 448 rule, and the scale is kept
+                q, s = ops.fp8_scaled_quantize(x)
+                self.input_scale.copy_(s)
+            else:
+                q, s = ops.fp8_scaled_quantize(x, scale=self.input_scale)
             y = ops.fp8_scaled_matmul(q, self.weight, s, self.w_scale, self.dtype, self.bias, b_packed=self.weight_packed)
         else:
             y = ops.matmul(x, self.weight, self.bias, b_packed=self.weight_packed)
@@ -153,6 +172,10 @@ class Qwen2DecoderLayer:
             assert tp_size % args.n_kv_heads == 0
             self.nkv, kv_ways, kv_piece = 1, args.n_kv_heads, tp_rank // (tp_size // args.n_kv_heads)
         self.d, self.args, self.mode, self.fuse, self.dtype = args.head_dim, args, mode, fuse and mode == "int8", dtype
+        # mode "fp8_static": static activation scales; fuse_fp8 = the producers emit the next linear's e4m3 operand (the attention
+        # epilogue for o_proj, the activation for down_proj, add + norm for the next layer's qkv_proj); False = the reference's
+        # operator order. Bit-identical either way.
+        self.fuse_fp8 = fuse and mode == "fp8_static"
         self.q_size, self.kv_size = self.nq * self.d, self.nkv * self.d
         H, I_full = args.hidden_size, args.intermediate_size
         I = I_full // tp_size
@@ -282,10 +305,79 @@ class Qwen2DecoderLayer:
             return None, residual, h_next
         return self.down_proj.forward(None, pre_quant=act_q), residual, None
 
+    # ---- mode "fp8_static" -----------------------------------------------------------------------------------------
+    def _norm_fp8_static(self, x, residual, w, lin: "QuantLinear", scale=None):
+        """apply_norm fused with the static e4m3 quantisation of the consuming linear's operand (qwen2_attention.cpp:204,
+        dense_mlp.cpp:137 get_fp8_input_scale -> fused_add_rms_norm_static_fp8_quant); returns ((e4m3, scale), residual).
+        While the model calibrates, the 16-bit norm: the linear then measures its own input."""
+        if lin is not None and lin.calibrating:
+            return self._norm(x, residual, w)
+        scale = lin.input_scale if scale is None else scale
+        q = torch.empty(x.shape, dtype=ops.FP8, device=x.device)
+        if residual is None:
+            ops.rms_norm_static_fp8_quant(q, x, w, scale, self.args.rms_norm_eps)
+            return (q, scale), x
+        ops.fused_add_rms_norm_static_fp8_quant(q, x, residual, w, scale, self.args.rms_norm_eps)
+        return (q, scale), residual
+
+    @staticmethod
+    def _lin(lin: "QuantLinear", h):
+        return lin.forward(None, pre_quant=h) if isinstance(h, tuple) else lin.forward(h)
+
+    def _forward_fp8_static(self, x, residual, positions, md: AttentionMetadata, kv_cache: KVCache, cos_sin, h_in, next_norm_w,
+                            next_input_scale):
+        """The layer on static activation scales. Unfused: the reference's operator order (norm + static quant fused for qkv_proj
+        and gate_up_proj, fp8_scaled_quantize(scale = input_scale) in front of o_proj and down_proj). Fused: RoPE + KV write in
+        one launch, the decode attention epilogue emits o_proj's operand (ops.paged_decode_attention_fp8), the activation emits
+        down_proj's (ops.act_and_mul_static_fp8_quant), and on the decode path the layer ends with the NEXT layer's add + norm +
+        static quant (h_next). Nine launches per decode layer instead of the 17 of mode "fp8". Same bits either way."""
+        fuse = self.fuse_fp8 and not self.qkv_proj.calibrating
+        decode = not (md.is_prefill or md.is_chunked_prefill)
+        if h_in is not None:
+            h = h_in
+        else:
+            h, residual = self._norm_fp8_static(x, residual, self.input_norm_w, self.qkv_proj)
+        qkv = self._lin(self.qkv_proj, h)
+        q = qkv[:, :self.q_size]
+        k = qkv[:, self.q_size:self.q_size + self.kv_size]
+        v = qkv[:, self.q_size + self.kv_size:]
+        if fuse:
+            ops.rotary_embedding_and_cache(positions, q, k, v, cos_sin, md.slot_mapping, kv_cache.k_cache, kv_cache.v_cache,
+                                           self.d, True)
+            s_o = self.o_proj.input_scale
+            if decode:
+                q8, _ = ops.paged_decode_attention_fp8(q.unflatten(-1, (self.nq, self.d)), kv_cache.k_cache, kv_cache.v_cache,
+                                                       md.kv_seq_lens, md.block_table, md.max_seq_len, self.attn.scale, s_o,
+                                                       self.attn.window_left)
+            else:   # prefill / chunked prefill: the attention kernels alone, then the static quantisation
+                attn, _ = self.attn.forward(md, q, k, v, kv_cache, kv_written=True)
+                q8 = torch.empty(attn.shape, dtype=ops.FP8, device=attn.device)
+                ops.static_scaled_fp8_quant(q8, attn, s_o)
+            x = self.o_proj.forward(None, pre_quant=(q8, s_o))
+        else:
+            ops.rotary_embedding(positions, q, k, cos_sin, True, head_size=self.d)
+            attn, _ = self.attn.forward(md, q, k, v, kv_cache)
+            x = self.o_proj.forward(attn)
+        h, residual = self._norm_fp8_static(x, residual, self.post_norm_w, self.gate_up_proj)
+        gate_up = self._lin(self.gate_up_proj, h)
+        if not fuse:
+            act = torch.empty(gate_up.size(0), self.I, dtype=gate_up.dtype, device=gate_up.device)
+            ops.act_and_mul(act, gate_up, "silu")
+            return self.down_proj.forward(act), residual, None
+        s_d = self.down_proj.input_scale
+        x = self.down_proj.forward(None, pre_quant=(ops.act_and_mul_static_fp8_quant(gate_up, s_d, "silu"), s_d))
+        if decode and next_norm_w is not None and next_input_scale is not None:
+            h_next, residual = self._norm_fp8_static(x, residual, next_norm_w, None, scale=next_input_scale)
+            return None, residual, h_next
+        return x, residual, None
+
     def forward(self, x, residual, positions, md: AttentionMetadata, kv_cache: KVCache, cos_sin, h_in=None,
-                next_norm_w=None, next_quant=True):
+                next_norm_w=None, next_quant=True, next_input_scale=None):
         """returns (x, residual, h_next): h_next is the NEXT layer's (or the model's final) norm output when this
-        layer's down_proj was fused with it (then x is None), else None."""
+        layer's down_proj was fused with it (then x is None), else None. next_input_scale (mode "fp8_static"): the next layer's
+        qkv_proj.input_scale, None in front of the model's final norm, which stays 16-bit."""
+        if self.mode == "fp8_static":
+            return self._forward_fp8_static(x, residual, positions, md, kv_cache, cos_sin, h_in, next_norm_w, next_input_scale)
         if h_in is not None:
             h = h_in                      # the previous layer already ran this layer's input norm (fused)
         else:
@@ -387,8 +479,9 @@ class Qwen2Model:
         for i, (layer, kvc) in enumerate(zip(self.layers, kv_caches)):
             last = i + 1 == n
             nxt = self.norm_w if last else self.layers[i + 1].input_norm_w
+            nxt_scale = None if last else self.layers[i + 1].qkv_proj.input_scale      # mode "fp8_static" only (else None)
             x, residual, h_in = layer.forward(x, residual, positions, md, kvc, self.cos_sin, h_in=h_in, next_norm_w=nxt,
-                                              next_quant=not last)
+                                              next_quant=not last, next_input_scale=nxt_scale)
         if h_in is not None:
             return h_in      # the last layer's down_proj already produced the final norm (16-bit)
         if residual is None:
@@ -398,6 +491,21 @@ class Qwen2Model:
             ops.fused_add_rms_norm(x, residual, self.norm_w, self.args.rms_norm_eps)
             out = x
         return out
+
+    def calibrate_fp8_static(self, tokens, positions, md: AttentionMetadata, kv_caches):
+        """mode "fp8_static": one forward in which every static-scale linear quantises its 16-bit input dynamically
+        (fp8_scaled_quantize's amax / 448 rule) and keeps the scale it used as its input_scale -- what a calibrated checkpoint
+        would carry. Deterministic; no host read (the scales stay on the device). Writes this step's K / V like any forward;
+        returns the hidden states of that forward."""
+        lins = [l for layer in self.layers for l in (layer.qkv_proj, layer.o_proj, layer.gate_up_proj, layer.down_proj)
+                if l.mode == "fp8_static"]
+        for l in lins:
+            l.calibrating = True
+        try:
+            return self.forward(tokens, positions, md, kv_caches)
+        finally:
+            for l in lins:
+                l.calibrating = False
 
     def logits(self, hidden):
         y = self.lm_head.forward(hidden)

@@ -1044,6 +1044,49 @@ def paged_decode_attention_int8(q, k_cache, v_cache, kv_seq_lens, block_table, m
     return oq, os_, o16
 
 
+# ------------------------------------------------------------------------------------------------ static-scale fp8 producers
+def act_and_mul_static_fp8_quant(input, scale, act_mode: str = "silu", out_q=None):
+    """act_and_mul followed by static_scaled_fp8_quant(scale) in one launch, byte for byte (xllm_mi355_act_and_mul_static_fp8_quant):
+    input [..., 2 * d] 16-bit, scale f32 [1] on the device -> e4m3 [T, d]; the 16-bit activation is never stored.
+    out_q: a contiguous one-byte [T, d] buffer to write instead of a new tensor."""
+    _need_cuda(input, scale)
+    if act_mode not in _ACT:
+        raise Mi355Error(f"Unsupported act mode: {act_mode}")
+    if not input.is_contiguous() or scale.dtype != torch.float32 or scale.numel() != 1:
+        raise Mi355Error("act_and_mul_static_fp8_quant: contiguous input, f32 [1] scale")
+    d = input.size(-1) // 2
+    T = input.numel() // (2 * d)
+    q = out_q if out_q is not None else torch.empty(T, d, dtype=FP8, device=input.device)
+    if q.numel() != T * d or q.element_size() != 1 or not q.is_contiguous():
+        raise Mi355Error("act_and_mul_static_fp8_quant: out_q must be a contiguous one-byte [T, d] tensor")
+    check(_lib.lib().xllm_mi355_act_and_mul_static_fp8_quant(_p(q), _p(input), _p(scale), T, d, _ACT[act_mode], _dt(input),
+                                                             _stream()), "act_and_mul_static_fp8_quant")
+    return q
+
+
+def paged_decode_attention_fp8(q, k_cache, v_cache, kv_seq_lens, block_table, max_kv_len, scale, out_scale, window_left=-1,
+                               want_16bit: bool = False, out_q=None):
+    """decode attention whose epilogue emits static_scaled_fp8_quant(out_scale) of its output (xllm_mi355_paged_decode_attention_fp8):
+    returns (e4m3 [B, nq * d], 16-bit out or None), the bytes of paged_attention(max_q_len=1) followed by static_scaled_fp8_quant.
+    Every launch plan is served; the workspace is paged_attention's. out_q: an e4m3 / uint8 [B, nq * d] buffer to write instead."""
+    _need_cuda(q, k_cache, v_cache, kv_seq_lens, block_table, out_scale)
+    B, nq, d = q.shape
+    n_blocks, bs, nkv, _ = k_cache.shape
+    if out_scale.dtype != torch.float32 or out_scale.numel() != 1:
+        raise Mi355Error("paged_decode_attention_fp8: out_scale must be f32 [1]")
+    oq = out_q if out_q is not None else torch.empty(B, nq * d, dtype=FP8, device=q.device)
+    if oq.numel() != B * nq * d or oq.element_size() != 1 or not oq.is_contiguous():
+        raise Mi355Error("paged_decode_attention_fp8: out_q must be a contiguous one-byte [B, nq * d] tensor")
+    o16 = torch.empty(B, nq * d, dtype=q.dtype, device=q.device) if want_16bit else None
+    bt = block_table if block_table.is_contiguous() else block_table.contiguous()
+    ws = _attn_workspace(q.device, _lib.lib().xllm_mi355_paged_attention_workspace_bytes(B, nq, d, 1, B))
+    check(_lib.lib().xllm_mi355_paged_decode_attention_fp8(
+        _p(q), _p(k_cache), _p(v_cache), _p(o16), _p(oq), _p(out_scale), _p(kv_seq_lens), _p(bt), bt.size(1), B, nq, nkv, d,
+        bs, n_blocks, q.stride(0), max_kv_len, scale, window_left, _dt(q), _p(ws), ws.numel(), _stream()),
+        "paged_decode_attention_fp8")
+    return oq, o16
+
+
 def decode_metadata_update(src: dict, dst: dict, actual_num_tokens: int, padded_num_tokens: int,
                            actual_batch_size: int, actual_indices_size: int, padded_batch_size: int = 0) -> None:
     """N2: refresh the persistent decode metadata of a captured graph on the device
