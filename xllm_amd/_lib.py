@@ -125,6 +125,13 @@ _SIGS = {
     "xllm_mi355_act_and_mul_static_fp8_quant": ([vp, vp, vp, i64, i64, ci, ci, vp], ci),
     "xllm_mi355_paged_decode_attention_fp8": ([vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, i64, i64,
                                                f32, i64, ci, vp, sz, vp], ci),
+    # csrc/xllm_mi355_kv_fp8.h
+    "xllm_mi355_reshape_paged_cache_kv8": ([vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, ci, vp], ci),
+    "xllm_mi355_rotary_embedding_and_cache_kv8": ([vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64,
+                                                   i64, i64, i64, ci, ci, vp], ci),
+    "xllm_mi355_paged_decode_attention_kv8": ([vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, i64, i64,
+                                               f32, i64, ci, vp, sz, vp], ci),
+    "xllm_mi355_paged_decode_kv8_plan": ([i64, i64, i64, i64, i64, i64, sz, vp, vp, vp, vp], ci),
 }
 # entry points declared in the header but implemented in a later build step are bound lazily
 _OPTIONAL = {

@@ -186,8 +186,22 @@ def build_attention_metadata(batch: BatchInput, is_prefill: bool, is_chunked_pre
 class KVCache:
     """framework/kv_cache: k/v caches [n_blocks, block_size, n_kv_heads_local, head_dim] (kv_cache_shape.cpp:239-267)"""
 
-    def __init__(self, k_cache: torch.Tensor, v_cache: torch.Tensor):
+    def __init__(self, k_cache: torch.Tensor, v_cache: torch.Tensor, k_scale: Optional[torch.Tensor] = None,
+                 v_scale: Optional[torch.Tensor] = None):
+        """k_scale / v_scale: device f32 [1], this layer's static scales of an e4m3 cache (torch.float8_e4m3fn caches: a code c
+        stands for float(c) * scale); None with 16-bit caches"""
         self.k_cache, self.v_cache = k_cache, v_cache
+        self.k_scale, self.v_scale = k_scale, v_scale
+        if self.is_fp8:
+            if v_cache is None or v_cache.dtype != ops.FP8:
+                raise ValueError("an e4m3 KVCache holds e4m3 K and V caches")
+            for s in (k_scale, v_scale):
+                if s is None or s.dtype != torch.float32 or s.numel() != 1 or s.device != k_cache.device:
+                    raise ValueError("an e4m3 KVCache needs k_scale and v_scale: f32 [1] on the cache's device")
+
+    @property
+    def is_fp8(self) -> bool:
+        return self.k_cache is not None and self.k_cache.dtype == ops.FP8
 
     def get_k_cache(self):
         return self.k_cache
@@ -215,6 +229,19 @@ class AttentionImpl:
         k = key.unflatten(-1, (self.num_kv_heads, self.head_size)) if key.dim() == 2 else key
         v = value.unflatten(-1, (self.num_kv_heads, self.head_size)) if value.dim() == 2 else value
         kc, vc = kv_cache.get_k_cache(), kv_cache.get_v_cache()
+        if getattr(kv_cache, "is_fp8", False):   # e4m3 cache with static scales: its own writer and decode operator
+            if md.is_chunked_prefill and not md.is_prefill:
+                raise NotImplementedError("chunked prefill over an e4m3 KV cache is out of scope: no kernel reads query chunks "
+                                          "against e4m3 pages yet (use a 16-bit cache for chunked prefill)")
+            if not kv_written:
+                ops.reshape_paged_cache_kv8(md.slot_mapping, k, v, kc, vc, kv_cache.k_scale, kv_cache.v_scale)
+            if md.is_prefill:   # reads this step's 16-bit k / v, not the cache
+                out = ops.prefill_attention(q, k, v, md.q_cu_seq_lens, md.kv_cu_seq_lens, md.max_query_len, self.scale,
+                                            True, self.window_left, out=output)
+            else:
+                out = ops.paged_attention_kv8(q, kc, vc, kv_cache.k_scale, kv_cache.v_scale, md.kv_seq_lens, md.block_table,
+                                              md.max_seq_len, self.scale, self.window_left, out=output)
+            return out, None
         if not kv_written:
             ops.reshape_paged_cache(md.slot_mapping, k, v, kc, vc)  # flash_attention.cpp:310-318
         if md.is_prefill:

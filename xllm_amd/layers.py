@@ -260,6 +260,20 @@ class Qwen2DecoderLayer:
                                             positions, cos_sin, md.slot_mapping, kv_cache.k_cache, kv_cache.v_cache, self.nq,
                                             self.nkv, self.d, self.dtype)
 
+    def _rope_cache_kv8(self, q, k, v, positions, md: AttentionMetadata, kv_cache: KVCache, cos_sin):
+        """e4m3 KV cache: RoPE + the quantising KV write in one launch (ops.rotary_embedding_and_cache_kv8). While the model
+        calibrates the cache's scales (Qwen2Model.calibrate_kv_scales) the rotated k and v are measured first: scale =
+        max(amax, 1e-12) / 448, written into the cache object's scale tensors in place, then the operator sequence."""
+        if getattr(kv_cache, "calibrating", False):
+            ops.rotary_embedding(positions, q, k, cos_sin, True, head_size=self.d)
+            for t, s in ((k, kv_cache.k_scale), (v, kv_cache.v_scale)):
+                s.copy_((torch.clamp(t.float().abs().amax(), min=1e-12) / 448.0).reshape(1))
+            ops.reshape_paged_cache_kv8(md.slot_mapping, k.unflatten(-1, (self.nkv, self.d)), v.unflatten(-1, (self.nkv, self.d)),
+                                        kv_cache.k_cache, kv_cache.v_cache, kv_cache.k_scale, kv_cache.v_scale)
+            return
+        ops.rotary_embedding_and_cache_kv8(positions, q, k, v, cos_sin, md.slot_mapping, kv_cache.k_cache, kv_cache.v_cache,
+                                           kv_cache.k_scale, kv_cache.v_scale, self.d, True)
+
     def pre_attention(self, x, residual, positions, md: AttentionMetadata, kv_cache: KVCache, cos_sin, h_in=None):
         """input norm (unless the previous layer fused it) + qkv_proj + RoPE + KV write; returns (q, residual)"""
         if h_in is not None:
@@ -341,7 +355,19 @@ class Qwen2DecoderLayer:
         q = qkv[:, :self.q_size]
         k = qkv[:, self.q_size:self.q_size + self.kv_size]
         v = qkv[:, self.q_size + self.kv_size:]
-        if fuse:
+        if getattr(kv_cache, "is_fp8", False):
+            # e4m3 KV cache: the fusions that write or read the cache in 16 bits are skipped -- RoPE + quantising KV write, the kv8
+            # decode operator (prefill reads this step's 16-bit k / v), then the static quantiser in front of o_proj
+            self._rope_cache_kv8(q, k, v, positions, md, kv_cache, cos_sin)
+            attn, _ = self.attn.forward(md, q, k, v, kv_cache, kv_written=True)
+            if fuse:
+                s_o = self.o_proj.input_scale
+                q8 = torch.empty(attn.shape, dtype=ops.FP8, device=attn.device)
+                ops.static_scaled_fp8_quant(q8, attn, s_o)
+                x = self.o_proj.forward(None, pre_quant=(q8, s_o))
+            else:
+                x = self.o_proj.forward(attn)
+        elif fuse:
             ops.rotary_embedding_and_cache(positions, q, k, v, cos_sin, md.slot_mapping, kv_cache.k_cache, kv_cache.v_cache,
                                            self.d, True)
             s_o = self.o_proj.input_scale
@@ -382,7 +408,9 @@ class Qwen2DecoderLayer:
             h = h_in                      # the previous layer already ran this layer's input norm (fused)
         else:
             h, residual = self._norm(x, residual, self.input_norm_w)
-        qkv = self._qkv_rope_cache(h, positions, md, kv_cache, cos_sin)   # small M: GEMM -> dequant + RoPE + KV write fused
+        kv8 = getattr(kv_cache, "is_fp8", False)   # e4m3 KV cache: none of the fusions that write or read the cache in 16 bits
+        # small M: GEMM -> dequant + RoPE + KV write fused
+        qkv = None if kv8 else self._qkv_rope_cache(h, positions, md, kv_cache, cos_sin)
         rope_done = qkv is not None
         if qkv is None:
             qkv = self.qkv_proj.forward(None, pre_quant=h) if self.fuse else self.qkv_proj.forward(h)
@@ -391,7 +419,12 @@ class Qwen2DecoderLayer:
         v = qkv[:, self.q_size + self.kv_size:]
         decode = not (md.is_prefill or md.is_chunked_prefill)
         fused_attn = None
-        if self.fuse and decode:
+        if kv8:
+            # qkv_proj -> RoPE + quantising KV write -> the kv8 decode operator (prefill: this step's 16-bit k / v); the mode's own
+            # quantiser in front of o_proj follows below (scaled_quantize / fp8_scaled_quantize inside the linear)
+            self._rope_cache_kv8(q, k, v, positions, md, kv_cache, cos_sin)
+            attn, _ = self.attn.forward(md, q, k, v, kv_cache, kv_written=True)
+        elif self.fuse and decode:
             # N1 fusions on the decode path: RoPE + KV write in one launch, and the attention epilogue emits the
             # int8 operand of o_proj directly (falls back when the batch is small enough to need split-KV)
             if not rope_done:
@@ -506,6 +539,20 @@ class Qwen2Model:
         finally:
             for l in lins:
                 l.calibrating = False
+
+    def calibrate_kv_scales(self, tokens, positions, md: AttentionMetadata, kv_caches):
+        """e4m3 KV caches: one forward in which every layer measures amax of its rotated k and of its v and stores
+        max(amax, 1e-12) / 448 (fp8_scaled_quantize's rule) into its cache's k_scale / v_scale tensors IN PLACE -- what a
+        checkpoint with static kv scales would carry. No host read; the step's K / V are written with the new scales. Returns the
+        hidden states of that forward."""
+        fp8 = [c for c in kv_caches if getattr(c, "is_fp8", False)]
+        for c in fp8:
+            c.calibrating = True
+        try:
+            return self.forward(tokens, positions, md, kv_caches)
+        finally:
+            for c in fp8:
+                c.calibrating = False
 
     def logits(self, hidden):
         y = self.lm_head.forward(hidden)

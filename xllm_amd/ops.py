@@ -43,11 +43,20 @@ def _need_cuda(*ts):
             raise Mi355Error("xllm_amd ops need device tensors (no CPU fallback on the product path)")
 
 
+def _no_fp8_cache(what: str, *caches):
+    """the 16-bit operators take `void*` caches and would misread an e4m3 one: refuse it before the C call"""
+    for c in caches:
+        if c is not None and c.dtype == FP8:
+            raise Mi355Error(f"{what}: the cache is float8_e4m3fn; an e4m3 KV cache is written by reshape_paged_cache_kv8 / "
+                             "rotary_embedding_and_cache_kv8 and read by paged_attention_kv8 only")
+
+
 # ------------------------------------------------------------------------------------------------ KV write
 def reshape_paged_cache(slot_ids, key, value, key_cache, value_cache) -> None:
     """kernel::reshape_paged_cache(ReshapePagedCacheParams&) (ops_api.h:31, reshape_paged_cache.cu:65-100)."""
     if (value is None) != (value_cache is None):
         raise Mi355Error("value and value_cache must both be given or both be None (K-only cache)")
+    _no_fp8_cache("reshape_paged_cache", key_cache, value_cache)
     _need_cuda(*[t for t in (slot_ids, key, value, key_cache, value_cache) if t is not None])
     if not (key.stride(-1) == 1 and key.stride(-2) == key.size(-1)) or (
             value is not None and not (value.stride(-1) == 1 and value.stride(-2) == value.size(-1))):
@@ -754,6 +763,7 @@ def paged_attention(q, k_cache, v_cache, cu_seqlens_q, kv_seq_lens, block_table,
     """prefix_decode_varlen_fwd argument set (layers/dcu/flash_attention.cpp:74-94, 220-288):
     q [Tq, nq, d] packed by cu_seqlens_q (None => one token per sequence); caches [n_blocks, bs, nkv, d]."""
     _need_cuda(q, k_cache, v_cache, kv_seq_lens, block_table)
+    _no_fp8_cache("paged_attention", k_cache, v_cache)
     Tq, nq, d = q.shape
     n_blocks, bs, nkv, _ = k_cache.shape
     B = kv_seq_lens.numel()
@@ -785,6 +795,7 @@ def paged_attention_shared_prefix(q, k_cache, v_cache, kv_seq_lens, block_table,
     that of paged_attention(q, ..., max_q_len=1) on the same tensors: q [B, nq, d], caches [n_blocks, bs, nkv, d], group_cu int32
     [n_groups + 1], group_prefix_blocks int32 [n_groups], all on the device -> out [B, nq * d]."""
     _need_cuda(q, k_cache, v_cache, kv_seq_lens, block_table, group_cu, group_prefix_blocks)
+    _no_fp8_cache("paged_attention_shared_prefix", k_cache, v_cache)
     B, nq, d = q.shape
     n_blocks, bs, nkv, _ = k_cache.shape
     if kv_seq_lens.numel() != B or group_cu.dtype != torch.int32 or group_prefix_blocks.dtype != torch.int32 or \
@@ -807,6 +818,7 @@ def mla_decode(q, k_cache, seqlens_k, block_table, head_size_v: int, scale: floa
     """flash_mla::dense_decode argument set (kernels/dcu/flash_mla_adapter.h:40-50): q [B, H, 576] =
     [q_nope*W_kc || q_pe], k_cache [n_blocks, block, 1, 576]; returns [B, H, head_size_v]."""
     _need_cuda(q, k_cache, seqlens_k, block_table)
+    _no_fp8_cache("mla_decode", k_cache)
     B, H, D = q.shape
     n_blocks, bs = k_cache.shape[0], k_cache.shape[1]
     o = out if out is not None else torch.empty(B, H, head_size_v, dtype=q.dtype, device=q.device)
@@ -828,6 +840,7 @@ def mla_prefill(q, k_cache, cu_seqlens_q, kv_seq_lens, block_table, head_size_v:
     """DeepseekV2AttentionImpl::prefill_sdpa (layers/dcu/deepseek_v2_attention.cpp:212-262) over the paged latent
     cache: q [T, H, 576], out [T, H, head_size_v]; bottom-right causal alignment."""
     _need_cuda(q, k_cache, cu_seqlens_q, kv_seq_lens, block_table)
+    _no_fp8_cache("mla_prefill", k_cache)
     T, H, D = q.shape
     if not q.is_contiguous() or not block_table.is_contiguous():
         raise Mi355Error("q and block_table must be contiguous")
@@ -979,6 +992,7 @@ def rotary_embedding_and_cache(positions, query, key, value, cos_sin_cache, slot
                                head_size: int, is_neox: bool = True) -> None:
     """apply_rotary + reshape_paged_cache in one launch (bit-identical to the two operators)."""
     _need_cuda(positions, query, key, value, cos_sin_cache, slot_ids, key_cache, value_cache)
+    _no_fp8_cache("rotary_embedding_and_cache", key_cache, value_cache)
     T = positions.numel()
     nq, nk = query.size(-1) // head_size, key.size(-1) // head_size
     check(_lib.lib().xllm_mi355_rotary_embedding_and_cache(
@@ -996,6 +1010,7 @@ def scaled_matmul_rope_cache(a, b_packed, a_scale, b_scale, bias, positions, cos
     (scaled_matmul + rotary_embedding_and_cache, bit for bit). Returns the packed qkv rows [M, N] with q and k rotated, or None
     when the shape is outside the fused path (the caller runs the separate operators)."""
     _need_cuda(a, b_packed, a_scale, b_scale, positions, cos_sin_cache, slot_ids, key_cache, value_cache)
+    _no_fp8_cache("scaled_matmul_rope_cache", key_cache, value_cache)
     M, K = a.shape
     N = (n_q_heads + 2 * n_kv_heads) * head_size
     if not _QKV_ROPE_FUSION or b_packed.numel() != N * K or not _prefer_packed(M, N, K) or cos_sin_cache.dtype != output_dtype:
@@ -1024,6 +1039,7 @@ def paged_decode_attention_int8(q, k_cache, v_cache, kv_seq_lens, block_table, m
     """decode attention whose epilogue also emits scaled_quantize of its output: returns (int8 [B, nq*d], scale [B],
     16-bit out or None), or None when the shape needs split-KV (caller falls back to paged_attention + quant)."""
     _need_cuda(q, k_cache, v_cache, kv_seq_lens, block_table)
+    _no_fp8_cache("paged_decode_attention_int8", k_cache, v_cache)
     B, nq, d = q.shape
     n_blocks, bs, nkv, _ = k_cache.shape
     oq = torch.empty(B, nq * d, dtype=torch.int8, device=q.device)
@@ -1070,6 +1086,7 @@ def paged_decode_attention_fp8(q, k_cache, v_cache, kv_seq_lens, block_table, ma
     returns (e4m3 [B, nq * d], 16-bit out or None), the bytes of paged_attention(max_q_len=1) followed by static_scaled_fp8_quant.
     Every launch plan is served; the workspace is paged_attention's. out_q: an e4m3 / uint8 [B, nq * d] buffer to write instead."""
     _need_cuda(q, k_cache, v_cache, kv_seq_lens, block_table, out_scale)
+    _no_fp8_cache("paged_decode_attention_fp8", k_cache, v_cache)
     B, nq, d = q.shape
     n_blocks, bs, nkv, _ = k_cache.shape
     if out_scale.dtype != torch.float32 or out_scale.numel() != 1:
@@ -1085,6 +1102,82 @@ def paged_decode_attention_fp8(q, k_cache, v_cache, kv_seq_lens, block_table, ma
         bs, n_blocks, q.stride(0), max_kv_len, scale, window_left, _dt(q), _p(ws), ws.numel(), _stream()),
         "paged_decode_attention_fp8")
     return oq, o16
+
+
+# ------------------------------------------------------------------------------------------------ e4m3 KV cache, static scales
+def _kv8_args(what, key_cache, value_cache, k_scale, v_scale):
+    for c in (key_cache, value_cache):
+        if c.element_size() != 1 or not c.is_contiguous() or c.dim() != 4:
+            raise Mi355Error(f"{what}: the caches are contiguous one-byte [n_blocks, block_size, n_kv_heads, head_dim] tensors")
+    for s in (k_scale, v_scale):
+        if s is None or s.dtype != torch.float32 or s.numel() != 1:
+            raise Mi355Error(f"{what}: k_scale and v_scale are f32 [1] tensors on the device")
+
+
+def reshape_paged_cache_kv8(slot_ids, key, value, key_cache, value_cache, k_scale, v_scale) -> None:
+    """KV write into an e4m3 cache (xllm_mi355_reshape_paged_cache_kv8): the bytes of static_scaled_fp8_quant(key, k_scale) /
+    (value, v_scale) scattered to the slots. key / value 16-bit [T, n_kv, d], token-strided views allowed."""
+    _need_cuda(slot_ids, key, value, key_cache, value_cache, k_scale, v_scale)
+    _kv8_args("reshape_paged_cache_kv8", key_cache, value_cache, k_scale, v_scale)
+    if not (key.stride(-1) == 1 and key.stride(-2) == key.size(-1)) or not (
+            value.stride(-1) == 1 and value.stride(-2) == value.size(-1)):
+        raise Mi355Error("keys/values must be contiguous over (n_kv_heads, head_dim)")
+    if slot_ids.dtype != torch.int32:
+        raise Mi355Error("slot_ids must be int32")
+    n_tokens, n_kv, d = key.shape[-3:]
+    check(_lib.lib().xllm_mi355_reshape_paged_cache_kv8(
+        _p(slot_ids), _p(key), _p(value), _p(key_cache), _p(value_cache), _p(k_scale), _p(v_scale), n_tokens, n_kv, d,
+        key_cache.size(-3), key_cache.size(0), key.stride(-3), value.stride(-3), _dt(key), _stream()), "reshape_paged_cache_kv8")
+
+
+def rotary_embedding_and_cache_kv8(positions, query, key, value, cos_sin_cache, slot_ids, key_cache, value_cache, k_scale,
+                                   v_scale, head_size: int, is_neox: bool = True) -> None:
+    """rotary_embedding (q, k in place, 16-bit) + the KV write of the rotated k and of v into an e4m3 cache in one launch: the
+    bytes of rotary_embedding -> static_scaled_fp8_quant -> scatter (xllm_mi355_rotary_embedding_and_cache_kv8)."""
+    _need_cuda(positions, query, key, value, cos_sin_cache, slot_ids, key_cache, value_cache, k_scale, v_scale)
+    _kv8_args("rotary_embedding_and_cache_kv8", key_cache, value_cache, k_scale, v_scale)
+    T = positions.numel()
+    nq, nk = query.size(-1) // head_size, key.size(-1) // head_size
+    check(_lib.lib().xllm_mi355_rotary_embedding_and_cache_kv8(
+        _p(positions), _p(query), _p(key), _p(value), _p(cos_sin_cache), _p(slot_ids), _p(key_cache), _p(value_cache),
+        _p(k_scale), _p(v_scale), T, nq, nk, head_size, cos_sin_cache.size(-1), query.stride(0), key.stride(0), value.stride(0),
+        key_cache.size(-3), key_cache.size(0), int(is_neox), _dt(query), _stream()), "rotary_embedding_and_cache_kv8")
+
+
+def paged_decode_kv8_plan(batch: int, n_q_heads: int, n_kv_heads: int, head_dim: int, block_size: int, max_kv_len: int,
+                          workspace_bytes: Optional[int] = None):
+    """xllm_mi355_paged_decode_kv8_plan: (hpw, nsplit_planned, nsplit, uniform) that paged_attention_kv8 takes for these scalars
+    (read-only, no launch, no device). workspace_bytes None = the bound paged_attention_kv8 itself provides."""
+    if workspace_bytes is None:
+        workspace_bytes = _lib.lib().xllm_mi355_paged_attention_workspace_bytes(batch, n_q_heads, head_dim, 1, batch)
+    v = [C.c_int32(-1) for _ in range(4)]
+    check(_lib.lib().xllm_mi355_paged_decode_kv8_plan(batch, n_q_heads, n_kv_heads, head_dim, block_size, max_kv_len,
+                                                      workspace_bytes, *[C.addressof(x) for x in v]), "paged_decode_kv8_plan")
+    return tuple(x.value for x in v)
+
+
+def paged_attention_kv8(q, k_cache, v_cache, k_scale, v_scale, kv_seq_lens, block_table, max_kv_len, scale, window_left=-1,
+                        out=None, workspace="auto"):
+    """Decode attention (one query token per sequence) over an e4m3 cache with static scales
+    (xllm_mi355_paged_decode_attention_kv8): q [B, nq, d] bf16 / f16, caches one-byte [n_blocks, bs, nkv, d], k_scale / v_scale
+    f32 [1] -> out [B, nq * d]. The result is decode attention over codes * scale. workspace: "auto" = the shared attention
+    scratch; None or a uint8 tensor = exactly that (split-KV degrades to what it holds)."""
+    _need_cuda(q, k_cache, v_cache, k_scale, v_scale, kv_seq_lens, block_table)
+    _kv8_args("paged_attention_kv8", k_cache, v_cache, k_scale, v_scale)
+    B, nq, d = q.shape
+    n_blocks, bs, nkv, _ = k_cache.shape
+    if kv_seq_lens.numel() != B:
+        raise Mi355Error("paged_attention_kv8: one query token per sequence")
+    o = out if out is not None else torch.empty(B, nq * d, dtype=q.dtype, device=q.device)
+    ws = workspace
+    if isinstance(workspace, str):
+        ws = _attn_workspace(q.device, _lib.lib().xllm_mi355_paged_attention_workspace_bytes(B, nq, d, 1, B))
+    bt = block_table if block_table.is_contiguous() else block_table.contiguous()
+    check(_lib.lib().xllm_mi355_paged_decode_attention_kv8(
+        _p(q), _p(k_cache), _p(v_cache), _p(k_scale), _p(v_scale), _p(o), _p(kv_seq_lens), _p(bt), bt.size(1), B, nq, nkv, d,
+        bs, n_blocks, q.stride(0), max_kv_len, scale, window_left, _dt(q), _p(ws), ws.numel() if ws is not None else 0,
+        _stream()), "paged_attention_kv8")
+    return o
 
 
 def decode_metadata_update(src: dict, dst: dict, actual_num_tokens: int, padded_num_tokens: int,
